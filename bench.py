@@ -12,6 +12,10 @@ seeded sequence `torch.Generator().manual_seed(0); randint(1, 50)` (mean 25), th
 N > 1: one process per GPU (torchrun env), weak scaling -- every rank runs its own step on its own
 noise; the only collective is the all-reduce of the flat LoRA gradient slab.  `value` is the
 whole-job rate: world_size * K / max-over-ranks wall time.
+
+A plain run sets up, warms up, times the K steps and prints the result line (`--dump-outputs DIR` also writes what the last
+timed step computed, and runs the steps in the deterministic mode so that two runs write the same arrays).  `--full` adds what takes runs of its own: the box calibration and the clock / power sampler, the same k
+sequence on the de-duplicated pass structure (`dedup`), the dominant-kernel roofline and the CPU baseline.
 """
 import argparse
 import json
@@ -473,6 +477,38 @@ def box_calibration(dev):
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs: everything it writes, together
+DUMP_SAMPLE = 1 << 20          # elements kept of an array that does not fit (seeded, sorted flat indices)
+
+
+def last_step_outputs(fused, net, args, loss):
+    """Device-side copies of what a caller of `FusedStep.step` holds after the step: the returned loss, the updated LoRA
+    parameters (fp32 master slab) and the gradient slab they were updated with, and the step's intermediate results on the
+    plans -- the target prediction, the three frozen predictions, the partially denoised latents."""
+    st = fused._state[(args.bs, args.res // 8, args.res // 8)]
+    last = st["last"]
+    out = {"loss": loss, "denoised_latents": st["x"], "pred_target": last["plan"].pred,
+           "lora_grad": net.grad, "lora_params": net.slab.detach()}
+    out.update({"pred_" + n: p for n, p in last["preds"].items()})
+    return {n: t.detach().clone() for n, t in out.items()}
+
+
+def write_outputs(folder, tensors, rank):
+    """DIR/<name>.npy (float32; rank r > 0 of a multi-GPU run: <name>.rank<r>.npy).  Arrays are written whole while the total
+    stays under DUMP_MAX_BYTES; otherwise the large ones as DUMP_SAMPLE elements at fixed seeded flat indices."""
+    import numpy as np
+    os.makedirs(folder, exist_ok=True)
+    arrs = {n: t.float().cpu().numpy() for n, t in tensors.items()}
+    if sum(a.nbytes for a in arrs.values()) > DUMP_MAX_BYTES:
+        for n, a in arrs.items():
+            if a.size > DUMP_SAMPLE:
+                idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))
+                arrs[n] = a.reshape(-1)[idx]
+    assert sum(a.nbytes for a in arrs.values()) <= DUMP_MAX_BYTES
+    for n, a in arrs.items():
+        np.save(os.path.join(folder, n + (f".rank{rank}" if rank else "") + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -498,9 +534,26 @@ def main():
     ap.add_argument("--telemetry-hz", type=float, default=10.0)
     ap.add_argument("--no-dedup", action="store_true",
                     help="skip the second timed loop (the de-duplicated pass structure, reported beside the headline as `dedup`)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: box calibration and the clock / power sampler, the second timed loop (`dedup`), "
+                         "the dominant-kernel roofline (per-launch isolation timing) and the CPU baseline -- each still subject "
+                         "to its own --no-* switch.  Without it a run sets up, warms up, times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the LAST timed step computed (loss, the four noise predictions, the "
+                         "denoised latents, the LoRA gradient slab and the updated LoRA parameters) as DIR/<name>.npy, float32.  Every input is seeded, and the run "
+                         "is made in the deterministic mode (no fp32 atomics in a step, somewhat slower; `config.deterministic` in "
+                         "the result line), so two runs with the same arguments write the same arrays.  LECO_DETERMINISTIC=0 in the "
+                         "environment keeps the default step: its outputs repeat to ~1e-2 only (DESIGN.md section 4)")
     ap.add_argument("--k", type=int, default=0, help="profiling only: fixed number of denoising passes per step "
                                                      "(0 = the seeded reference distribution; the headline number uses 0)")
     args = ap.parse_args()
+    if args.dump_shapes and not args.full:
+        ap.error("--dump-shapes is written by the dominant-kernel accounting: it needs --full")
+    if args.dump_outputs:
+        # outputs that two runs (or two builds) can be compared by: the default step sums GroupNorm statistics and LoRA weight
+        # gradients with fp32 atomics, and bf16 layers amplify the order of those sums to ~1e-2 between two replays
+        # An explicit LECO_DETERMINISTIC in the environment is the caller's choice and stands.
+        os.environ.setdefault("LECO_DETERMINISTIC", "1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: re-launch this script as N ranks (one process per GPU) under torchrun
@@ -605,7 +658,7 @@ def main():
 
     # clocks / power / throttle state before, during (sampler thread) and after the timed loop (tools/gpu_telemetry.py)
     tele = None
-    if not emu and not args.no_telemetry and rank == 0:
+    if args.full and not emu and not args.no_telemetry and rank == 0:
         try:
             sys.path.insert(0, os.path.join(ROOT, "tools"))
             from gpu_telemetry import Telemetry
@@ -614,7 +667,7 @@ def main():
             tele = None
             print(f"telemetry unavailable: {e!r}", file=sys.stderr)
     tele_idle = tele.snapshot() if tele else None
-    box = box_calibration(dev) if (not emu and rank == 0 and not args.no_telemetry) else None
+    box = box_calibration(dev) if (args.full and not emu and rank == 0 and not args.no_telemetry) else None
     for i in range(args.warmup):
         one(i)
     barrier()
@@ -641,11 +694,13 @@ def main():
     if tele:
         tele_samples = tele.stop()
         tele_after = tele.snapshot()
+    # what the last timed step left behind, copied on the device before anything else runs on these buffers
+    dumped = last_step_outputs(fused, net, args, losses[-1]) if args.dump_outputs and args.steps > 0 else None
     # ---- the same k sequence once more on the DE-DUPLICATED pass structure (FusedStep.dedup, what train() runs unless
     # --strict_reference): reported beside the headline, never as the headline -- the headline executes the reference's own
     # k + 3 + 1 CFG-doubled passes.  Two untimed steps first (plan build + graph capture).
     dedup_out = None
-    if not args.no_dedup and not args.dominant_only:
+    if args.full and not args.no_dedup:
         fused.dedup = True
         for i in range(min(2, args.warmup + args.steps)):
             one(i)
@@ -691,6 +746,8 @@ def main():
         shutdown_distributed()
     losses = [float(l.item()) for l in losses]
     finite = all(math.isfinite(l) for l in losses)
+    if dumped is not None:
+        write_outputs(args.dump_outputs, dumped, rank)
     if rank != 0:
         if not finite:
             sys.exit(f"rank {rank}: non-finite loss in the timed steps: {losses}")
@@ -710,7 +767,7 @@ def main():
                                f"{args.res}x{args.res}, prompt batch {args.bs} (UNet batch {2 * args.bs}), DDIM 50, "
                                f"reference-faithful pass structure (k+3+1 fwd, 1 bwd)",
                    "global_batch": args.bs * world, "k_sequence_seed": 0 if args.k <= 0 else f"fixed k={args.k} (profiling run)", "k_mean": sum(timed_ks) / len(timed_ks),
-                   "hip_graphs": bool(unet.use_graphs), "parallelism": f"dp{world}", "loss": losses[-1], "losses": losses,
+                   "hip_graphs": bool(unet.use_graphs), "deterministic": bool(unet.engine().deterministic), "parallelism": f"dp{world}", "loss": losses[-1], "losses": losses,
                    "collectives_per_step": collectives / args.steps, "k_identical_across_ranks": ks_same},
     }
     if dedup_out is not None:
@@ -748,36 +805,42 @@ def main():
         out["telemetry"] = {"idle_before_warmup": tele_idle, "before_timed": tele_before, "after_timed": tele_after,
                             "during_timed": Telemetry.summarize(tele_samples, t0, t1_host),
                             "accumulated_over_timed": Telemetry.delta(tele_before, tele_after), "sampler_hz": args.telemetry_hz}
-    try:
-        if args.no_dominant or emu:
-            raise RuntimeError("--no-dominant")
-        st = fused._state[(args.bs, args.res // 8, args.res // 8)]
-        if tele:
-            tele.start(args.telemetry_hz)
+
+    def whole_step_roofline(kernel):      # no dominant-kernel figures: the whole-step fraction stands in
+        return {"bound": "mfma", "achieved": whole["achieved"], "peak": whole["peak"], "unit": "TFLOP/s",
+                "frac": whole["frac"], "traffic": None, "whole_step": whole, "kernel": kernel}
+    if not args.full:
+        out["roofline"] = whole_step_roofline({"skipped": "the per-launch isolation timing runs with --full"})
+    else:
         try:
-            dom = dominant_kernel_roofline(st, sum(timed_ks) / len(timed_ks), dump_shapes=args.dump_shapes,
-                                           headline_workload=(args.arch == "sd15" and args.bs == 2 and args.res == 512 and args.rank == 4
-                                                              and not args.c3lier and not args.v_pred))
-        finally:
-            if tele:   # clocks while the launches were timed in isolation (bursts): the reference point for the loop's clocks
-                out["telemetry"]["during_isolated_launch_timing"] = Telemetry.summarize(tele.stop())
-        iso = dom.get("isolated_us")
-        if iso:
-            # busy fraction per step: isolated GPU time of the launches the step issues (fixed lists + k denoising passes) over
-            # the step's measured time.  Uniformly low with low clocks in `telemetry` = DVFS; dips on single steps = launch path
-            busy = [(iso["fixed"] + k * iso["per_denoise_pass"]) * 1e-3 / m for k, m in zip(timed_ks, step_ms)]
-            out["timing"]["gpu_busy_frac"] = [round(b, 4) for b in busy]
-            out["timing"]["gpu_busy_frac_mean"] = sum(busy) / len(busy)
-            out["timing"]["isolated_launch_sum_ms_per_step"] = sum(iso["fixed"] + k * iso["per_denoise_pass"] for k in timed_ks) * 1e-3 / len(timed_ks)
-        # the roofline object is the DOMINANT KERNEL's (algorithmic FLOPs per launch / its average launch duration);
-        # the whole-step figure rides along
-        out["roofline"] = {"bound": "mfma", "achieved": dom["achieved"], "peak": dom["peak"], "unit": "TFLOP/s",
-                           "frac": dom["frac"], "traffic": dom.get("traffic"), "kernel": dom, "whole_step": whole,
-                           "hbm_bound": dom.pop("hbm_bound", None)}
-    except Exception as e:  # never hide the step number
-        out["roofline"] = {"bound": "mfma", "achieved": whole["achieved"], "peak": whole["peak"], "unit": "TFLOP/s",
-                           "frac": whole["frac"], "traffic": None, "whole_step": whole, "kernel": {"error": repr(e)}}
-    if world == 1 and not args.no_cpu_baseline and not emu:
+            if args.no_dominant or emu:
+                raise RuntimeError("--no-dominant")
+            st = fused._state[(args.bs, args.res // 8, args.res // 8)]
+            if tele:
+                tele.start(args.telemetry_hz)
+            try:
+                dom = dominant_kernel_roofline(st, sum(timed_ks) / len(timed_ks), dump_shapes=args.dump_shapes,
+                                               headline_workload=(args.arch == "sd15" and args.bs == 2 and args.res == 512 and args.rank == 4
+                                                                  and not args.c3lier and not args.v_pred))
+            finally:
+                if tele:   # clocks while the launches were timed in isolation (bursts): the reference point for the loop's clocks
+                    out["telemetry"]["during_isolated_launch_timing"] = Telemetry.summarize(tele.stop())
+            iso = dom.get("isolated_us")
+            if iso:
+                # busy fraction per step: isolated GPU time of the launches the step issues (fixed lists + k denoising passes) over
+                # the step's measured time.  Uniformly low with low clocks in `telemetry` = DVFS; dips on single steps = launch path
+                busy = [(iso["fixed"] + k * iso["per_denoise_pass"]) * 1e-3 / m for k, m in zip(timed_ks, step_ms)]
+                out["timing"]["gpu_busy_frac"] = [round(b, 4) for b in busy]
+                out["timing"]["gpu_busy_frac_mean"] = sum(busy) / len(busy)
+                out["timing"]["isolated_launch_sum_ms_per_step"] = sum(iso["fixed"] + k * iso["per_denoise_pass"] for k in timed_ks) * 1e-3 / len(timed_ks)
+            # the roofline object is the DOMINANT KERNEL's (algorithmic FLOPs per launch / its average launch duration);
+            # the whole-step figure rides along
+            out["roofline"] = {"bound": "mfma", "achieved": dom["achieved"], "peak": dom["peak"], "unit": "TFLOP/s",
+                               "frac": dom["frac"], "traffic": dom.get("traffic"), "kernel": dom, "whole_step": whole,
+                               "hbm_bound": dom.pop("hbm_bound", None)}
+        except Exception as e:  # never hide the step number
+            out["roofline"] = whole_step_roofline({"error": repr(e)})
+    if args.full and world == 1 and not args.no_cpu_baseline and not emu:
         try:
             out["cpu_baseline"] = cpu_baseline(sum(timed_ks) / len(timed_ks), args.bs)
         except Exception as e:  # the baseline leg must never hide the GPU number

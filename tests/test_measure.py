@@ -172,3 +172,27 @@ def test_gpu_telemetry_degrades_to_fields_and_summarises():
     assert s["throttle_flags_seen"] == ["4"]
     d = Telemetry.delta({"ppt_residency_acc": 10, "energy_accumulator": 5}, {"ppt_residency_acc": 25, "energy_accumulator": 9})
     assert d == {"ppt_residency_acc": 15, "energy_accumulator": 4}
+
+
+def test_bench_dump_outputs_samples_large_arrays_at_fixed_indices(tmp_path):
+    """bench.write_outputs above the 64 MB limit (SDXL rank 16: 42.5 M-element slabs): arrays over DUMP_SAMPLE elements are
+    written as DUMP_SAMPLE elements at sorted flat indices that are the same on every call, small arrays whole, everything
+    float32, the total within the limit; under the limit nothing is sampled."""
+    import numpy as np
+    import bench
+    big = torch.arange(9 << 20, dtype=torch.float32)             # 36 MB each: two of them exceed the limit
+    small = torch.arange(1000, dtype=torch.float32).to(torch.bfloat16)
+    for d in ("a", "b"):
+        bench.write_outputs(str(tmp_path / d), {"lora_grad": big, "lora_params": big + 0.5, "loss": small}, 0)
+    total = 0
+    for f in ("lora_grad.npy", "lora_params.npy", "loss.npy"):
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float32 and np.array_equal(a, b), f
+        total += a.nbytes
+    assert total <= bench.DUMP_MAX_BYTES
+    g, p_, l = (np.load(tmp_path / "a" / f) for f in ("lora_grad.npy", "lora_params.npy", "loss.npy"))
+    assert g.shape == (bench.DUMP_SAMPLE,) and np.all(np.diff(g) > 0) and 0 <= g[0] and g[-1] < big.numel()   # values = indices
+    assert np.array_equal(p_, g + 0.5)                            # the same indices for arrays of the same size
+    assert np.array_equal(l, small.float().numpy())               # small arrays are written whole
+    bench.write_outputs(str(tmp_path / "r1"), {"x": big}, 1)      # under the limit: whole; rank r > 0 carries its rank
+    assert np.array_equal(np.load(tmp_path / "r1" / "x.rank1.npy"), big.numpy())

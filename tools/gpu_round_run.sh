@@ -32,7 +32,7 @@ python $R/tools/pmc_summary.py /tmp/pmc_mfma > $O/${RN}_pmc_mfma_step.csv 2>&1
 timeout 110 rocprofv3 --kernel-trace --output-format csv --pmc FETCH_SIZE -d /tmp/pmc_fetch -o bench -- python $R/bench.py --steps 1 --warmup 0 --k 4 --no-cpu-baseline --no-graphs --no-dominant --no-dedup > /tmp/pmc2.log 2>&1
 python $R/tools/pmc_summary.py /tmp/pmc_fetch > $O/${RN}_pmc_fetch_step.csv 2>&1
 cd $R
-( timeout 900 python bench.py --steps 20 --warmup 5 --dump-shapes $O/${RN}_dominant_shapes.txt 2>/dev/null | tail -1 ) > $O/${RN}_bench.json
+( timeout 900 python bench.py --full --steps 20 --warmup 5 --dump-shapes $O/${RN}_dominant_shapes.txt 2>/dev/null | tail -1 ) > $O/${RN}_bench.json
 ( timeout 150 python tools/plan_profile.py --list denoise --top 45 2>/dev/null ) > $O/${RN}_plan_denoise.txt
 ( timeout 150 python tools/plan_profile.py --list frozen --top 30 2>/dev/null ) > $O/${RN}_plan_frozen.txt
 ( timeout 100 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -3 ) > $O/${RN}_smoke.log 2>&1
@@ -66,10 +66,10 @@ timeout 250 python tools/tune_report.py --arch sdxl --res 1024 --bs 1 --rank 16 
 timeout 200 python tools/tune_report.py --arch sd15 --res 512 --bs 4 --rank 8 --c3lier --out $T > $O/${RN}_tune_c3lier.txt 2>/dev/null; tail -2 $O/${RN}_tune_c3lier.txt
 timeout 300 python tools/tune_report.py --arch sd15 --res 512 --bs 2 --rank 4 --dedup --out $T > $O/${RN}_tune_sd15.txt 2>/dev/null; tail -2 $O/${RN}_tune_sd15.txt
 cp $T $O/gemm_tune_gfx950.json
-( timeout 400 python bench.py --arch sd21 --res 768 --v-pred --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 ) > $O/${RN}_bench_sd21_768.json
-( timeout 600 python bench.py --arch sdxl --res 1024 --bs 1 --rank 16 --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 ) > $O/${RN}_bench_sdxl_1024.json
-( timeout 400 python bench.py --bs 4 --rank 8 --c3lier --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 ) > $O/${RN}_bench_sd15_c3lier_bs4.json
-( timeout 200 python bench.py --no-cpu-baseline --no-dominant 2>/dev/null | tail -1 ) > $O/${RN}_bench_after_tune.json
+( timeout 400 python bench.py --full --arch sd21 --res 768 --v-pred --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 ) > $O/${RN}_bench_sd21_768.json
+( timeout 600 python bench.py --full --arch sdxl --res 1024 --bs 1 --rank 16 --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 ) > $O/${RN}_bench_sdxl_1024.json
+( timeout 400 python bench.py --full --bs 4 --rank 8 --c3lier --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 ) > $O/${RN}_bench_sd15_c3lier_bs4.json
+( timeout 200 python bench.py --full --no-cpu-baseline --no-dominant 2>/dev/null | tail -1 ) > $O/${RN}_bench_after_tune.json
 for f in ${RN}_bench_sd21_768 ${RN}_bench_sdxl_1024 ${RN}_bench_sd15_c3lier_bs4 ${RN}_bench_after_tune; do python - $O/$f.json <<'PY'
 import json,sys
 try:
@@ -79,9 +79,9 @@ PY
 done
 fi
 if [ "$what" = "configs_bench" ]; then      # BASELINE configs 3-5, 20 timed steps, full accounting, the committed launch-shape table (no re-tuning)
-( timeout 400 python bench.py --arch sd21 --res 768 --v-pred --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 ) > $O/${RN}_bench_sd21_768.json
-( timeout 600 python bench.py --arch sdxl --res 1024 --bs 1 --rank 16 --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 ) > $O/${RN}_bench_sdxl_1024.json
-( timeout 400 python bench.py --bs 4 --rank 8 --c3lier --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 ) > $O/${RN}_bench_sd15_c3lier_bs4.json
+( timeout 400 python bench.py --full --arch sd21 --res 768 --v-pred --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 ) > $O/${RN}_bench_sd21_768.json
+( timeout 600 python bench.py --full --arch sdxl --res 1024 --bs 1 --rank 16 --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 ) > $O/${RN}_bench_sdxl_1024.json
+( timeout 400 python bench.py --full --bs 4 --rank 8 --c3lier --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 ) > $O/${RN}_bench_sd15_c3lier_bs4.json
 for f in ${RN}_bench_sd21_768 ${RN}_bench_sdxl_1024 ${RN}_bench_sd15_c3lier_bs4; do python - $O/$f.json <<'PY'
 import json,sys
 try:
@@ -91,9 +91,9 @@ PY
 done
 fi
 if [ "$what" = "configs_quick" ]; then      # BASELINE configs 3-5 with the committed launch-shape table (no re-tuning)
-( timeout 200 python bench.py --arch sd21 --res 768 --v-pred --steps 6 --warmup 2 --no-cpu-baseline --no-dominant 2>/dev/null | tail -1 ) > $O/${RN}_bench_sd21_768.json
-( timeout 300 python bench.py --arch sdxl --res 1024 --bs 1 --rank 16 --steps 6 --warmup 2 --no-cpu-baseline --no-dominant 2>/dev/null | tail -1 ) > $O/${RN}_bench_sdxl_1024.json
-( timeout 200 python bench.py --bs 4 --rank 8 --c3lier --steps 6 --warmup 2 --no-cpu-baseline --no-dominant 2>/dev/null | tail -1 ) > $O/${RN}_bench_sd15_c3lier_bs4.json
+( timeout 200 python bench.py --full --arch sd21 --res 768 --v-pred --steps 6 --warmup 2 --no-cpu-baseline --no-dominant 2>/dev/null | tail -1 ) > $O/${RN}_bench_sd21_768.json
+( timeout 300 python bench.py --full --arch sdxl --res 1024 --bs 1 --rank 16 --steps 6 --warmup 2 --no-cpu-baseline --no-dominant 2>/dev/null | tail -1 ) > $O/${RN}_bench_sdxl_1024.json
+( timeout 200 python bench.py --full --bs 4 --rank 8 --c3lier --steps 6 --warmup 2 --no-cpu-baseline --no-dominant 2>/dev/null | tail -1 ) > $O/${RN}_bench_sd15_c3lier_bs4.json
 for f in ${RN}_bench_sd21_768 ${RN}_bench_sdxl_1024 ${RN}_bench_sd15_c3lier_bs4; do python - $O/$f.json <<'PY'
 import json,sys
 try:

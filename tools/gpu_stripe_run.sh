@@ -13,8 +13,8 @@ tail -6 $O/${RN}_stripe_tests.log
 ( LECO_STRIPE=0 timeout 200 python tools/plan_profile.py --list frozen --top 60 2>&1 | tail -80 ) > $O/${RN}_plan_frozen_nostripe.txt
 head -3 $O/${RN}_plan_denoise_stripe.txt; grep xblock $O/${RN}_plan_denoise_stripe.txt; head -1 $O/${RN}_plan_denoise_nostripe.txt
 head -1 $O/${RN}_plan_frozen_stripe.txt; grep xblock $O/${RN}_plan_frozen_stripe.txt; head -1 $O/${RN}_plan_frozen_nostripe.txt
-( timeout 300 python bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-dominant 2>&1 | tail -1 ) > $O/${RN}_bench_stripe_short.json
-( LECO_STRIPE=0 timeout 300 python bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-dominant 2>&1 | tail -1 ) > $O/${RN}_bench_nostripe_short.json
+( timeout 300 python bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-dominant 2>&1 | tail -1 ) > $O/${RN}_bench_stripe_short.json
+( LECO_STRIPE=0 timeout 300 python bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-dominant 2>&1 | tail -1 ) > $O/${RN}_bench_nostripe_short.json
 for f in ${RN}_bench_stripe_short ${RN}_bench_nostripe_short; do python - $O/$f.json <<'PY'
 import json,sys
 try:

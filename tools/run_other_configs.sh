@@ -11,9 +11,9 @@ timeout 250 python tools/tune_report.py --arch sdxl --res 1024 --bs 1 --rank 16 
 timeout 200 python tools/tune_report.py --arch sd15 --res 512 --bs 4 --rank 8 --c3lier --out $T > $O/r02_tune_c3lier.txt 2>/dev/null; tail -2 $O/r02_tune_c3lier.txt
 cp $T $O/gemm_tune_gfx950.json
 fi
-( timeout 200 python bench.py --arch sd21 --res 768 --v-pred --steps 6 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 ) > $O/r02_bench_sd21_768.json
-( timeout 300 python bench.py --arch sdxl --res 1024 --bs 1 --rank 16 --steps 6 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 ) > $O/r02_bench_sdxl_1024.json
-( timeout 200 python bench.py --bs 4 --rank 8 --c3lier --steps 6 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 ) > $O/r02_bench_sd15_c3lier_bs4.json
+( timeout 200 python bench.py --full --arch sd21 --res 768 --v-pred --steps 6 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 ) > $O/r02_bench_sd21_768.json
+( timeout 300 python bench.py --full --arch sdxl --res 1024 --bs 1 --rank 16 --steps 6 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 ) > $O/r02_bench_sdxl_1024.json
+( timeout 200 python bench.py --full --bs 4 --rank 8 --c3lier --steps 6 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 ) > $O/r02_bench_sd15_c3lier_bs4.json
 for f in r02_bench_sd21_768 r02_bench_sdxl_1024 r02_bench_sd15_c3lier_bs4; do python - $O/$f.json <<'PY'
 import json,sys
 try:

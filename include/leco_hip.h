@@ -310,6 +310,31 @@ int leco_adamw(float* p, const float* g, float* m, float* v, void* shadow, const
  * bf16 shadow refresh as leco_adamw. */
 int leco_lion(float* p, const float* g, float* m, void* shadow, const float* hyper, float beta1, float beta2,
               float wd, int64_t n, leco_stream_t stream);
+/* Prodigy (Mishchenko & Defazio 2023, as released in prodigyopt 1.0; selected by train.optimizer = "prodigy",
+ * train_util.py:366-370): Adam whose step size d lr is ESTIMATED -- d grows from d0 by the ratio of two sums over ALL
+ * parameters, so `lr` stays at 1.  The reference's prepare_optimizer_params() is one param group: one pass over the flat
+ * slab is the published algorithm.  g = grad_scale * grad (+ weight_decay p when not decoupled),
+ *   bc   = bias correction ? sqrt(1 - beta2^(k+1)) / (1 - beta1^(k+1)) : 1,   dlr = d lr bc   (d BEFORE this step)
+ *   lr > 0:  num = beta3 d_numerator + (d/d0) dlr sum g (p0 - p)
+ *            exp_avg = beta1 exp_avg + d (1-beta1) g,  exp_avg_sq = beta2 exp_avg_sq + d^2 (1-beta2) g^2
+ *            s = beta3 s + (d/d0) (safeguard warmup ? d : dlr) g,  den = sum |s|        (lr <= 0: den = 0)
+ *   den == 0: p, d, k stay (d_numerator keeps the decayed value).  Otherwise, for lr > 0: d_hat = d_coef num / den,
+ *            d = max(d, d_hat) while d is still d0, d_max = max(d_max, d_hat), d = min(d_max, d growth_rate); then
+ *   p *= 1 - weight_decay dlr (decoupled),  p -= dlr exp_avg / (sqrt(exp_avg_sq) + d eps)   (NEW d, this step's dlr),  k += 1.
+ * Two launches, no host round trip: the first updates exp_avg / exp_avg_sq / s and reduces the two sums (per-block
+ * partials added in a fixed order by the last block to finish: bitwise reproducible, so data-parallel replicas derive the
+ * same d) and updates *state; the second applies the update and refreshes the bf16 shadow.  The scalars are doubles:
+ * d_numerator is an exponentially weighted sum over thousands of steps of terms that start near d0 = 1e-6 (the package
+ * holds it as a Python float).  Start a run from {d0, d0, d0, 0, 0, d0, 0, 0}.  s, p0 (fp32 [n], caller-owned like the
+ * moments): s starts at 0, p0 holds the parameters at the first Prodigy step.  hyper (device): {lr, -, -, grad_scale}.
+ * beta3: the package's default is sqrt(beta2).  growth_rate may be +inf.  Launches on one device must be stream-ordered. */
+typedef struct leco_prodigy_state {
+    double d, d0, d_max, d_numerator, d_denom, d_hat, dlr, k;
+} leco_prodigy_state;
+enum { LECO_PRODIGY_DECOUPLE = 1, LECO_PRODIGY_BIAS_CORRECTION = 2, LECO_PRODIGY_SAFEGUARD_WARMUP = 4 };
+int leco_prodigy(float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* s, const float* p0, void* shadow,
+                 const float* hyper, leco_prodigy_state* state, double beta1, double beta2, double beta3, double eps,
+                 double weight_decay, double d_coef, double growth_rate, int32_t flags, int64_t n, leco_stream_t stream);
 int leco_cast_f32_bf16(const float* x, void* y, int64_t n, leco_stream_t stream);
 int leco_memset(void* p, int32_t value, int64_t bytes, leco_stream_t stream);
 /* dst = `reps` copies of the `bytes` (multiple of 16) at src, back to back: batch broadcast of a tensor that is identical for

@@ -1,6 +1,6 @@
 // HBM-bound elementwise / small kernels of the LECO step: GEGLU, conv_in / conv_out (the two
 // convolutions that are not GEMM-shaped: Cin = 4 and Cout = 4), timestep sinusoid, gradient adds,
-// 2x2 upsample dgrad, CFG-combine + DDIM update, ESD loss + its gradient, fused AdamW.
+// 2x2 upsample dgrad, CFG-combine + DDIM update, ESD loss + its gradient, fused AdamW / Lion / Prodigy.
 // All bf16 traffic is moved as 16-byte vectors (8 x bf16 per lane); latent-sized tensors
 // ((bs,4,h,w), a few hundred KB) stay fp32.
 #include <errno.h>
@@ -517,6 +517,140 @@ __global__ __launch_bounds__(256) void lion_kernel(float* p, const float* g, flo
     }
 }
 
+// ---- Prodigy (Mishchenko & Defazio 2023, as released in prodigyopt 1.0) over the flat LoRA slab ----------------------
+// One param group and a GLOBAL step-size estimate d: one pass over the slab IS the published algorithm.  hyper =
+// {lr, -, -, grad_scale}; the scalar state (leco_prodigy_state, eight doubles: d_numerator is an exponentially weighted
+// sum over thousands of steps of terms that start near d0 = 1e-6) lives on the device, so a step never meets the host.
+// Launch A: moments, s and the two sums  sum g (p0 - p),  sum |s|.  Each block leaves its two partials in g_prodigy_part
+// and draws a ticket; the block that draws the last one adds the partials in a FIXED order (fixed grid + fixed order: the
+// step is bitwise reproducible, so data-parallel replicas that see the same all-reduced gradient derive the same d),
+// updates the state and re-arms the ticket.  Launch B: the parameter update from the state, and the bf16 shadow.
+// The scratch is per device: launches must be stream-ordered (they are: one optimizer step per training step).
+constexpr int PRODIGY_BLOCKS = 8192;                   // grid_for's cap
+__device__ double g_prodigy_part[2 * PRODIGY_BLOCKS];
+__device__ unsigned g_prodigy_ticket = 0;
+struct ProdigyConst {
+    double beta1, beta2, beta3, eps, wd, d_coef, growth;
+    int flags;
+};
+__device__ __forceinline__ double shfl_xor_f64(double v, int mask) {      // the two halves travel as bit patterns
+    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
+    const float lo = shfl_xor(__builtin_bit_cast(float, (unsigned)(u & 0xffffffffull)), mask);
+    const float hi = shfl_xor(__builtin_bit_cast(float, (unsigned)(u >> 32)), mask);
+    return __builtin_bit_cast(double, ((unsigned long long)__builtin_bit_cast(unsigned, hi) << 32) |
+                                          (unsigned long long)__builtin_bit_cast(unsigned, lo));
+}
+__device__ __forceinline__ double prodigy_dlr(const leco_prodigy_state* st, double lr, const ProdigyConst& c) {
+    double bc = 1.0;
+    if (c.flags & LECO_PRODIGY_BIAS_CORRECTION) bc = sqrt(1.0 - pow(c.beta2, st->k + 1.0)) / (1.0 - pow(c.beta1, st->k + 1.0));
+    return st->d * lr * bc;
+}
+// sums of a and b over the 256 threads of the block, in a fixed order (xor butterfly in each wave, then the four wave totals);
+// the result is valid in thread 0
+__device__ __forceinline__ void prodigy_block_sum(double& a, double& b, double (&red)[2][4]) {
+#pragma unroll
+    for (int mk = 32; mk >= 1; mk >>= 1) {
+        a += shfl_xor_f64(a, mk);
+        b += shfl_xor_f64(b, mk);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        red[0][threadIdx.x >> 6] = a;
+        red[1][threadIdx.x >> 6] = b;
+    }
+    __syncthreads();
+    a = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+    b = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+}
+__global__ __launch_bounds__(256) void prodigy_moments_kernel(const float* p, const float* g, float* m, float* v, float* s,
+                                                               const float* p0, const float* hyper, leco_prodigy_state* st,
+                                                               ProdigyConst c, int64_t n) {
+    __shared__ double red[2][4];
+    __shared__ double coef[4];
+    __shared__ bool last;
+    const double lr = (double)hyper[0];
+    if (threadIdx.x == 0) {          // block-uniform scalars: one pair of double pow per block, not per thread
+        const double d = st->d, dlr = prodigy_dlr(st, lr, c);
+        coef[0] = d * (1.0 - c.beta1);
+        coef[1] = d * d * (1.0 - c.beta2);
+        coef[2] = (d / st->d0) * ((c.flags & LECO_PRODIGY_SAFEGUARD_WARMUP) ? d : dlr);
+        coef[3] = dlr;
+    }
+    __syncthreads();
+    const float gs = hyper[3], b1 = (float)c.beta1, b2 = (float)c.beta2, b3 = (float)c.beta3;
+    const float cm = (float)coef[0], cv = (float)coef[1], cs = (float)coef[2];
+    const float cwd = (c.flags & LECO_PRODIGY_DECOUPLE) ? 0.f : (float)c.wd;
+    double num = 0.0, den = 0.0;
+    if (lr > 0.0) {
+        for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
+            const float pv = p[e];
+            float gr = g[e] * gs;
+            if (cwd != 0.f) gr += cwd * pv;
+            num += (double)gr * (double)(p0[e] - pv);
+            m[e] = b1 * m[e] + cm * gr;
+            v[e] = b2 * v[e] + cv * (gr * gr);
+            const float ss = b3 * s[e] + cs * gr;
+            s[e] = ss;
+            den += (double)fabsf(ss);
+        }
+    }
+    prodigy_block_sum(num, den, red);
+    if (threadIdx.x == 0) {
+        g_prodigy_part[2 * blockIdx.x] = num;
+        g_prodigy_part[2 * blockIdx.x + 1] = den;
+        __threadfence();                                               // partials visible device-wide before the ticket
+        last = atomicAdd(&g_prodigy_ticket, 1u) == gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!last) return;                                                 // (block-uniform)
+    // The last block adds the partials in a FIXED order: thread t takes blocks t, t + 256, ... in ascending order, then the
+    // block reduction above.  (One thread walking every partial pair in block order is a chain of dependent trips to L2:
+    // measured 1.77 ms with 6 624 blocks.)
+    __threadfence();
+    double tn = 0.0, td = 0.0;
+    for (unsigned b = threadIdx.x; b < gridDim.x; b += 256) {
+        tn += ((volatile double*)g_prodigy_part)[2 * b];
+        td += ((volatile double*)g_prodigy_part)[2 * b + 1];
+    }
+    __syncthreads();                                                   // thread 0 is done with `red`
+    prodigy_block_sum(tn, td, red);
+    if (threadIdx.x == 0) {           // every block has read the state before it drew its ticket: it may change now
+        double d = st->d;
+        const double dlr = coef[3];
+        st->dlr = dlr;
+        st->d_denom = td;
+        if (lr > 0.0) {
+            const double dn = c.beta3 * st->d_numerator + (d / st->d0) * dlr * tn;
+            st->d_numerator = dn;
+            if (td != 0.0) {
+                const double d_hat = c.d_coef * dn / td;
+                if (d == st->d0) d = fmax(d, d_hat);
+                const double d_max = fmax(st->d_max, d_hat);
+                st->d_hat = d_hat;
+                st->d_max = d_max;
+                st->d = fmin(d_max, d * c.growth);
+            }
+        }
+        if (td != 0.0) st->k += 1.0;
+        g_prodigy_ticket = 0;                                          // re-armed for the next (stream-ordered) launch
+    }
+}
+// p *= 1 - wd dlr (decoupled), p -= dlr m / (sqrt(v) + d eps): the NEW d in the denominator, the step's own dlr.
+// d_denom == 0 (all-zero gradients so far, or lr <= 0): the step did not happen, p stays.
+__global__ __launch_bounds__(256) void prodigy_apply_kernel(float* p, const float* m, const float* v, bf16_t* shadow,
+                                                             const leco_prodigy_state* st, ProdigyConst c, int64_t n) {
+    const bool live = st->d_denom != 0.0;
+    const float dlr = (float)st->dlr, deps = (float)(st->d * c.eps);
+    const float keep = (c.flags & LECO_PRODIGY_DECOUPLE) ? (float)(1.0 - c.wd * st->dlr) : 1.f;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
+        float pv = p[e];
+        if (live) {
+            pv = pv * keep - dlr * (m[e] / (sqrtf(v[e]) + deps));
+            p[e] = pv;
+        }
+        shadow[e] = f2bf(pv);
+    }
+}
+
 __global__ __launch_bounds__(256) void cast_f32_bf16_kernel(const float* x, bf16_t* y, int64_t n) {
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) y[e] = f2bf(x[e]);
 }
@@ -855,6 +989,25 @@ extern "C" int leco_lion(float* p, const float* g, float* m, void* shadow, const
     hipLaunchKernelGGL(lion_kernel, dim3(grid_for(n)), dim3(256), 0, LECO_STREAM, p, g, m, (bf16_t*)shadow, hyper, beta1,
                        beta2, wd, n);
     return check_launch("leco_lion");
+}
+extern "C" int leco_prodigy(float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* s, const float* p0,
+                            void* shadow, const float* hyper, leco_prodigy_state* state, double beta1, double beta2,
+                            double beta3, double eps, double weight_decay, double d_coef, double growth_rate, int32_t flags,
+                            int64_t n, leco_stream_t stream) {
+    if (!p || !g || !exp_avg || !exp_avg_sq || !s || !p0 || !shadow || !hyper || !state || n <= 0)
+        return fail(-EINVAL, "leco_prodigy: null operand or n=%lld <= 0", (long long)n);
+    if (flags & ~(LECO_PRODIGY_DECOUPLE | LECO_PRODIGY_BIAS_CORRECTION | LECO_PRODIGY_SAFEGUARD_WARMUP))
+        return fail(-EINVAL, "leco_prodigy: unknown flag bits 0x%x", (unsigned)flags);
+    if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && beta3 >= 0.0 && beta3 < 1.0) || !(eps >= 0.0) ||
+        !(d_coef > 0.0) || !(growth_rate >= 1.0))
+        return fail(-EINVAL, "leco_prodigy: betas must be in [0, 1), eps >= 0, d_coef > 0, growth_rate >= 1");
+    const ProdigyConst c{beta1, beta2, beta3, eps, weight_decay, d_coef, growth_rate, flags};
+    const int grid = grid_for(n);                 // <= PRODIGY_BLOCKS: one partial pair per block; a function of n alone
+    hipLaunchKernelGGL(prodigy_moments_kernel, dim3(grid), dim3(256), 0, LECO_STREAM, (const float*)p, g, exp_avg, exp_avg_sq,
+                       s, p0, hyper, state, c, n);
+    hipLaunchKernelGGL(prodigy_apply_kernel, dim3(grid), dim3(256), 0, LECO_STREAM, p, (const float*)exp_avg,
+                       (const float*)exp_avg_sq, (bf16_t*)shadow, (const leco_prodigy_state*)state, c, n);
+    return check_launch("leco_prodigy");
 }
 extern "C" int leco_cast_f32_bf16(const float* x, void* y, int64_t n, leco_stream_t stream) {
     hipLaunchKernelGGL(cast_f32_bf16_kernel, dim3(grid_for(n)), dim3(256), 0, LECO_STREAM, x, (bf16_t*)y, n);

@@ -16,7 +16,7 @@ import torch
 from . import hip
 from .hip import ACT_NONE, ACT_SILU, A_PLAIN, GemmArgs, LoraSite, ptr  # noqa: F401
 
-_vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
+_vp, _i32, _i64, _f32, _f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
 
 _SIGS = {
     "leco_groupnorm_fwd": [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _i64, _vp],
@@ -45,6 +45,7 @@ _SIGS = {
     "leco_esd_loss_cond": [_vp, _vp, _vp, _vp, _f32, _f32, _i64, _vp, _vp, _vp],
     "leco_adamw": [_vp, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _i64, _vp],
     "leco_lion": [_vp, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _i64, _vp],
+    "leco_prodigy": [_vp] * 9 + [_f64] * 7 + [_i32, _i64, _vp],
     "leco_cast_f32_bf16": [_vp, _vp, _i64, _vp],
     "leco_memset": [_vp, _i32, _i64, _vp],
     "leco_repeat": [_vp, _vp, _i64, _i32, _vp],
@@ -286,6 +287,27 @@ def adamw(p, g, m, v, shadow, hyper, beta1, beta2, eps, wd, n) -> Op:
 
 def lion(p, g, m, shadow, hyper, beta1, beta2, wd, n) -> Op:
     return Op("leco_lion", (ptr(p), ptr(g), ptr(m), ptr(shadow), ptr(hyper), beta1, beta2, wd, n))
+
+
+PRODIGY_DECOUPLE, PRODIGY_BIAS_CORRECTION, PRODIGY_SAFEGUARD_WARMUP = 1, 2, 4
+PRODIGY_STATE_FIELDS = ("d", "d0", "d_max", "d_numerator", "d_denom", "d_hat", "dlr", "k")   # leco_prodigy_state
+
+
+def prodigy_state(d0: float, device) -> torch.Tensor:
+    """A fresh `leco_prodigy_state` (eight doubles) on `device`."""
+    return torch.tensor([d0, d0, d0, 0.0, 0.0, d0, 0.0, 0.0], dtype=torch.float64, device=device)
+
+
+def prodigy(p, g, m, v, s, p0, shadow, hyper, state, beta1, beta2, beta3, eps, wd, d_coef, growth_rate, decouple,
+            use_bias_correction, safeguard_warmup, n) -> Op:
+    """Two launches: moments + s + the two global sums + the scalar state, then the parameter update + bf16 shadow."""
+    if state.dtype != torch.float64 or state.numel() != len(PRODIGY_STATE_FIELDS):
+        raise ValueError("prodigy: state must be the 8 doubles of leco_prodigy_state (ops.prodigy_state)")
+    flags = ((PRODIGY_DECOUPLE if decouple else 0) | (PRODIGY_BIAS_CORRECTION if use_bias_correction else 0)
+             | (PRODIGY_SAFEGUARD_WARMUP if safeguard_warmup else 0))
+    return Op("leco_prodigy", (ptr(p), ptr(g), ptr(m), ptr(v), ptr(s), ptr(p0), ptr(shadow), ptr(hyper), ptr(state),
+                               float(beta1), float(beta2), float(beta3), float(eps), float(wd), float(d_coef),
+                               float(growth_rate), flags, n), keep=(s, p0, state))
 
 
 def cast_f32_bf16(x, y, n) -> Op:

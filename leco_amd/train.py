@@ -17,7 +17,7 @@ save cadence and file names.  The per-step arithmetic (train_lora.py:141-290) is
   5. backward plan (dgrad through the UNet, wgrad of LoRA down/up only) into the flat fp32
      gradient slab;
   6. data parallel: ONE all-reduce (RCCL over xGMI) of that slab -- no other collective;
-  7. fused AdamW on the flat fp32 master slab, refreshing the bf16 shadow the kernels read.
+  7. fused AdamW (or Lion / Prodigy) on the flat fp32 master slab, refreshing the bf16 shadow the kernels read.
 
 Nothing in a step synchronises with the host; ``loss`` is a device scalar.
 """
@@ -126,16 +126,33 @@ class FusedStep:
 
     def __init__(self, unet, network: LoRANetwork, scheduler, max_denoising_steps: int = 50, lr: float = 1e-4,
                  betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, world_size: int = 1,
-                 process_group=None, optimizer="adamw", dedup: bool = False):
+                 process_group=None, optimizer="adamw", dedup: bool = False, prodigy: Optional[dict] = None):
         """``optimizer``: "adamw" / "adam" (fused leco_adamw; adam = no decoupled decay), "lion" (fused leco_lion),
-        or a ``torch.optim.Optimizer`` built on ``network.prepare_optimizer_params()`` (its ``step()`` runs on the
-        fp32 slab views, then the bf16 shadow is refreshed)."""
+        "prodigy" (fused leco_prodigy; ``prodigy``: its keywords, `PRODIGY_DEFAULTS` -- ``betas`` / ``eps`` default to
+        this constructor's arguments, ``weight_decay`` to Prodigy's own 0 unless the dict carries it; ``lr`` is the
+        multiplier of the estimated step size, normally 1.0), or a ``torch.optim.Optimizer`` built on ``network.prepare_optimizer_params()`` (its ``step()``
+        runs on the fp32 slab views, then the bf16 shadow is refreshed)."""
         self.unet, self.net, self.sched = unet, network, scheduler
         self.optimizer = optimizer
         self.n_steps = max_denoising_steps
         self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
         self.world, self.pg = world_size, process_group
         self.opt_step = 0
+        self.prodigy = None
+        self._prodigy_buf = None           # (s, p0, leco_prodigy_state): allocated at the first use, this optimizer only
+        self._prodigy_p0_taken = False     # p0 holds the parameters of the first Prodigy step (or a resumed run's)
+        if isinstance(optimizer, str) and optimizer == "prodigy":
+            unknown = set(prodigy or {}) - set(PRODIGY_KEYS)
+            if unknown:
+                raise ValueError(f"prodigy: unsupported keyword(s) {sorted(unknown)}; the fused kernel implements {PRODIGY_KEYS}")
+            cfg = dict(PRODIGY_DEFAULTS, betas=tuple(betas), eps=eps)
+            cfg.update(prodigy or {})
+            cfg["betas"] = tuple(cfg["betas"])
+            if cfg["beta3"] is None:
+                cfg["beta3"] = math.sqrt(cfg["betas"][1])
+            self.prodigy = cfg
+        elif prodigy is not None:
+            raise ValueError('`prodigy` keywords need optimizer="prodigy"')
         dev = unet.device
         self.dev = dev
         # device-side schedule tables
@@ -510,6 +527,15 @@ class FusedStep:
         elif self.optimizer == "lion":
             ops.lion(net.slab.detach(), net.grad, net.exp_avg, net.shadow, net.hyper, b1, b2, self.wd,
                      net.slab.numel()).run()
+        elif self.optimizer == "prodigy":
+            c = self.prodigy
+            s, p0, state = self._prodigy_buffers()
+            if not self._prodigy_p0_taken:       # the first Prodigy step: x_0 of the distance estimate
+                p0.copy_(net.slab.detach())
+                self._prodigy_p0_taken = True
+            ops.prodigy(net.slab.detach(), net.grad, net.exp_avg, net.exp_avg_sq, s, p0, net.shadow, net.hyper, state,
+                        c["betas"][0], c["betas"][1], c["beta3"], c["eps"], c["weight_decay"], c["d_coef"], c["growth_rate"],
+                        c["decouple"], c["use_bias_correction"], c["safeguard_warmup"], net.slab.numel()).run()
         else:   # any torch optimizer over the slab views (prodigy, dadapt*, 8-bit ... when their packages exist)
             if self.world > 1:
                 net.grad.mul_(1.0 / self.world)
@@ -521,7 +547,27 @@ class FusedStep:
             net.sync_shadow()
         net.mark_updated()
 
+    def _prodigy_buffers(self):
+        """Prodigy's slab-sized `s` and `p0` and its device scalar state (ops.prodigy_state)."""
+        if self.prodigy is None:
+            raise RuntimeError('this FusedStep was not built with optimizer="prodigy"')
+        slab = self.net.slab.detach()
+        buf = self._prodigy_buf
+        if buf is None or buf[0].shape != slab.shape or buf[0].device != slab.device:
+            buf = self._prodigy_buf = (torch.zeros_like(slab), torch.empty_like(slab), ops.prodigy_state(self.prodigy["d0"], slab.device))
+            self._prodigy_p0_taken = False
+        return buf
 
+    def prodigy_state(self) -> dict:
+        """Prodigy's scalars {d, d0, d_max, d_numerator, d_denom, d_hat, dlr, k} (dlr = d * lr * bias correction of the
+        last step).  Copies them from the device, i.e. waits for the queued steps: for tests and logging."""
+        return dict(zip(ops.PRODIGY_STATE_FIELDS, self._prodigy_buffers()[2].cpu().tolist()))
+
+
+# optimizer_args the fused Prodigy implements (prodigyopt.Prodigy's keywords; `lr` is train.lr)
+PRODIGY_DEFAULTS = dict(betas=(0.9, 0.999), beta3=None, eps=1e-8, weight_decay=0.0, decouple=True, use_bias_correction=False,
+                        safeguard_warmup=False, d0=1e-6, d_coef=1.0, growth_rate=float("inf"))
+PRODIGY_KEYS = tuple(PRODIGY_DEFAULTS)
 
 STATE_KEYS = ("slab", "exp_avg", "exp_avg_sq")
 
@@ -553,6 +599,11 @@ def save_training_state(path, fused: "FusedStep", iteration: int, lr_scheduler=N
     blob.update(format=2, world_size=int(fused.world), opt_step=fused.opt_step, iteration=int(iteration), rng=rngs,
                 lr_scheduler=None if lr_scheduler is None else lr_scheduler.state_dict(),
                 optimizer=None if isinstance(fused.optimizer, str) else fused.optimizer.state_dict())
+    if fused.prodigy is not None:    # the fused Prodigy: its two extra slabs and the scalar state (other optimizers: format 2 as ever)
+        s, p0, state = fused._prodigy_buffers()
+        if not fused._prodigy_p0_taken:      # saved before the first step: x_0 is the slab as it stands
+            p0 = net.slab.detach()
+        blob.update(format=3, prodigy=dict(s=s.cpu().clone(), p0=p0.cpu().clone(), state=state.cpu().clone()))
     torch.save(blob, path)
 
 
@@ -578,9 +629,24 @@ def load_training_state(path, fused: "FusedStep", lr_scheduler=None) -> int:
     if has_obj_state == isinstance(fused.optimizer, str):
         raise ValueError(f"{path}: saved with {'an optimizer object' if has_obj_state else 'the fused optimizer kernel'}, this "
                          f"run uses {'the fused optimizer kernel' if has_obj_state else 'an optimizer object'}: same config needed")
+    pz = blob.get("prodigy")
+    if (pz is not None) != (fused.prodigy is not None):
+        raise ValueError(f"{path}: saved {'by the fused Prodigy optimizer' if pz is not None else 'without Prodigy state'}, this run "
+                         f"uses optimizer={fused.optimizer if isinstance(fused.optimizer, str) else type(fused.optimizer).__name__!r}"
+                         ": same config needed")
+    if pz is not None:
+        for k in ("s", "p0"):
+            if tuple(pz[k].shape) != tuple(net.slab.shape) or pz[k].dtype != torch.float32:
+                raise ValueError(f"{path}: prodigy.{k} has shape {tuple(pz[k].shape)}, the network's slab {tuple(net.slab.shape)}")
+        if pz["state"].dtype != torch.float64 or pz["state"].numel() != len(ops.PRODIGY_STATE_FIELDS):
+            raise ValueError(f"{path}: prodigy.state is not the {len(ops.PRODIGY_STATE_FIELDS)} doubles of leco_prodigy_state")
     with torch.no_grad():
         for k in STATE_KEYS:
             getattr(net, k).detach().copy_(blob[k].to(getattr(net, k).device))
+        if pz is not None:
+            for dst, k in zip(fused._prodigy_buffers(), ("s", "p0", "state")):
+                dst.copy_(pz[k].to(dst.device))
+            fused._prodigy_p0_taken = True
     fused.opt_step = int(blob["opt_step"])
     if has_obj_state:
         fused.optimizer.load_state_dict(blob["optimizer"])
@@ -701,6 +767,10 @@ def train(config: RootConfig, prompts: List[PromptSettings], device: Optional[to
         unsupported = set(optimizer_kwargs) - {"betas", "eps", "weight_decay"}
         coupled_l2 = opt_name == "adam" and optimizer_kwargs.get("weight_decay", 0.0)
         fused_opt = opt_name if not (coupled_l2 or unsupported) else None
+    elif opt_name == "prodigy" and not strict_reference:
+        # fused on the flat slab (leco_prodigy) when every keyword is one the kernel implements; anything else (slice_p, ...)
+        # goes to the package like before -- nothing is dropped silently
+        fused_opt = opt_name if set(optimizer_kwargs) <= set(PRODIGY_KEYS) else None
     else:
         fused_opt = None
     if strict_reference and weight_dtype != torch.float32:
@@ -715,7 +785,9 @@ def train(config: RootConfig, prompts: List[PromptSettings], device: Optional[to
     fused = FusedStep(unet, network, noise_scheduler, config.train.max_denoising_steps, lr=config.train.lr,
                       betas=tuple(optimizer_kwargs.get("betas", default_betas)), eps=optimizer_kwargs.get("eps", 1e-8),
                       weight_decay=optimizer_kwargs.get("weight_decay", wd_default), world_size=world,
-                      optimizer=fused_opt, dedup=dedup)
+                      optimizer=fused_opt, dedup=dedup,
+                      prodigy={k: v for k, v in optimizer_kwargs.items() if k not in ("betas", "eps")}
+                      if fused_opt == "prodigy" else None)
     # LR schedule: drive torch's own scheduler objects on a dummy parameter so the values are exact
     _dummy = torch.optim.SGD([torch.nn.Parameter(torch.zeros(1))], lr=config.train.lr)
     lr_scheduler = train_util.get_lr_scheduler(config.train.lr_scheduler, _dummy, max_iterations=config.train.iterations,
@@ -798,10 +870,14 @@ def train(config: RootConfig, prompts: List[PromptSettings], device: Optional[to
         latents = train_util.get_initial_latents(noise_scheduler, pair.batch_size, height, width, 1)
         add_time_ids = train_util.get_add_time_ids(height, width, dynamic_crops=pair.dynamic_crops) if xl else None
         loss = fused.step(pair, timesteps_to, latents, lr=lr_scheduler.get_last_lr()[0], add_time_ids=add_time_ids)
-        if pbar is not None and (i % 10 == 0 or config.logging.verbose):
-            pbar.set_description(f"Loss*1k: {loss.item() * 1000:.4f}")
+        show = pbar is not None and (i % 10 == 0 or config.logging.verbose)
+        # (the loss already waits for the step where it is shown: Prodigy's estimated step size d * lr comes along, fetched once)
+        dlr = fused.prodigy_state()["dlr"] if fused.prodigy and (show or wandb is not None) else None
+        if show:
+            pbar.set_description(f"Loss*1k: {loss.item() * 1000:.4f}" + ("" if dlr is None else f" d*lr: {dlr:.3e}"))
         if wandb is not None:
-            wandb.log({"loss": loss.item(), "iteration": i, "lr": lr_scheduler.get_last_lr()[0]})
+            wandb.log({"loss": loss.item(), "iteration": i, "lr": lr_scheduler.get_last_lr()[0],
+                       **({} if dlr is None else {"d*lr": dlr})})
         _dummy.step()
         lr_scheduler.step()
         if i % config.save.per_steps == 0 and i != 0 and i != config.train.iterations - 1:

@@ -1,0 +1,91 @@
+#!/usr/bin/env python
+"""Sampling script for SD1.x / SD2.x -- `examples/infer_xl.py` for the non-XL models.
+
+`model_util.load_models` -> `train_util.encode_prompts` for the prompt and the negative prompt -> `concat_embeddings` ->
+`get_initial_latents` -> `train_util.diffusion` (DDIM, classifier-free guidance) through the HIP UNet, optionally with a
+trained LoRA applied (`--lora out/x_last.safetensors`, the file `train_lora.py` writes).  The latents go to a safetensors
+file (`--out`); with `--image PATH` they are decoded by the HIP VAE decoder (`leco_amd/vae.py`) and saved as a PNG, as
+the reference's `test/infer_xl.py:136-154` does for SDXL.
+
+    python examples/infer.py --model synthetic:tiny --height 128 --width 128 --steps 4 --image out.png
+    python examples/infer.py --model /models/sd21 --v2 --v_pred --height 768 --width 768 --lora output/x_last.safetensors --image x.png
+"""
+import argparse
+import contextlib
+import importlib.util
+import io
+import os
+import sys
+
+import torch
+from safetensors.torch import save_file
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+from leco_amd import model_util, train_util  # noqa: E402
+from leco_amd.lora import LoRANetwork  # noqa: E402
+
+
+def _write_image(*a, **k):
+    spec = importlib.util.spec_from_file_location("infer_xl", os.path.join(HERE, "infer_xl.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod.write_image(*a, **k)
+
+
+@torch.no_grad()
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="synthetic:tiny")
+    ap.add_argument("--v2", action="store_true")
+    ap.add_argument("--v_pred", action="store_true")
+    ap.add_argument("--prompt", default="a photo of lemonade")
+    ap.add_argument("--negative_prompt", default="")
+    ap.add_argument("--height", type=int, default=512)
+    ap.add_argument("--width", type=int, default=512)
+    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--guidance_scale", type=float, default=7.5)
+    ap.add_argument("--lora", default=None, help="LoRA weights saved by train_lora.py")
+    ap.add_argument("--rank", type=int, default=4)
+    ap.add_argument("--alpha", type=float, default=1.0)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--no_graphs", action="store_true", help="eager launches instead of one hipGraph per UNet pass")
+    ap.add_argument("--out", default="latents.safetensors")
+    ap.add_argument("--image", default=None, help="decode the latents with the VAE and write this PNG")
+    ap.add_argument("--vae", default=None, help="VAE for --image (default: the model's vae/ folder, or its synthetic VAE)")
+    args = ap.parse_args(argv)
+    dev = torch.device(args.device)
+    dtype = torch.bfloat16
+    tokenizer, text_encoder, unet, sched = model_util.load_models(args.model, scheduler_name="ddim", v2=args.v2, v_pred=args.v_pred)
+    text_encoder.to(dev, dtype=dtype)
+    text_encoder.eval()
+    unet.to(dev, dtype=dtype)
+    unet.enable_xformers_memory_efficient_attention()
+    unet.requires_grad_(False)
+    unet.eval()
+    unet.use_graphs = dev.type == "cuda" and not args.no_graphs
+    network = None
+    if args.lora:
+        with contextlib.redirect_stdout(io.StringIO()):
+            network = LoRANetwork(unet, rank=args.rank, multiplier=1.0, alpha=args.alpha).to(dev)
+        network.load_weights(args.lora)
+    pos = train_util.encode_prompts(tokenizer, text_encoder, [args.prompt])
+    neg = train_util.encode_prompts(tokenizer, text_encoder, [args.negative_prompt])
+    text_embeds = train_util.concat_embeddings(neg, pos, 1)
+    sched.set_timesteps(args.steps, device=dev)
+    torch.manual_seed(args.seed)
+    latents = train_util.get_initial_latents(sched, 1, args.height, args.width, 1).to(dev, dtype=dtype)
+    with (network if network is not None else contextlib.nullcontext()):
+        latents = train_util.diffusion(unet, sched, latents, text_embeds, total_timesteps=args.steps, start_timesteps=0,
+                                       guidance_scale=args.guidance_scale)
+    save_file({"latents": latents.float().cpu().contiguous()}, args.out,
+              {"prompt": args.prompt, "steps": str(args.steps), "guidance_scale": str(args.guidance_scale)})
+    print(f"Done. latents {tuple(latents.shape)} -> {args.out}")
+    if args.image:
+        _write_image(latents, args.vae or args.model, args.image, dev, use_graphs=unet.use_graphs)
+    return latents
+
+
+if __name__ == "__main__":
+    main()

@@ -6,12 +6,13 @@ Same flow: `model_util.load_models_xl` -> `train_util.encode_prompts_xl` for the
 offset) -> `train_util.diffusion_xl` (DDIM, classifier-free guidance 7) through the HIP UNet, optionally with a trained
 LoRA applied (`--lora out/x_last.safetensors`, the file `train_lora_xl.py` writes).
 
-The reference then decodes the latents with diffusers' `AutoencoderKL` and saves a PNG; the VAE is not part of the
-training hot path and is not implemented here, so this script stops at the latents and writes them to a safetensors
-file (`--out`), which any diffusers VAE decodes as `vae.decode(latents / vae.config.scaling_factor)`.
+The latents are written to a safetensors file (`--out`).  With `--image PATH` the script goes on as the reference does
+(:136-154): `vae.decode(latents / scaling_factor)`, denormalise, save a PNG -- through the HIP VAE decoder
+(`leco_amd/vae.py`; `--vae` names the VAE: a diffusers folder, a single-file checkpoint or `synthetic:...`; default: the
+model's own `vae/` folder, or the synthetic VAE of a synthetic model).  Without `--image` nothing about the VAE is loaded.
 
-    python examples/infer_xl.py --model synthetic:tiny_xl --height 128 --width 128 --steps 4
-    python examples/infer_xl.py --model /models/sdxl-base --lora output/x_last.safetensors --prompt "a photo of lemonade"
+    python examples/infer_xl.py --model synthetic:tiny_xl --height 128 --width 128 --steps 4 --image out.png
+    python examples/infer_xl.py --model /models/sdxl-base --lora output/x_last.safetensors --prompt "a photo of lemonade" --image lemonade.png
 """
 import argparse
 import contextlib
@@ -46,6 +47,8 @@ def main(argv=None):
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--no_graphs", action="store_true", help="eager launches instead of one hipGraph per UNet pass")
     ap.add_argument("--out", default="latents.safetensors")
+    ap.add_argument("--image", default=None, help="decode the latents with the VAE and write this PNG")
+    ap.add_argument("--vae", default=None, help="VAE for --image (default: the model's vae/ folder, or its synthetic VAE)")
     args = ap.parse_args(argv)
     dev = torch.device(args.device)
     dtype = torch.bfloat16
@@ -80,7 +83,21 @@ def main(argv=None):
     save_file({"latents": latents.float().cpu().contiguous()}, args.out,
               {"prompt": args.prompt, "steps": str(args.steps), "guidance_scale": str(args.guidance_scale)})
     print(f"Done. latents {tuple(latents.shape)} -> {args.out}")
+    if args.image:
+        write_image(latents, args.vae or args.model, args.image, dev, use_graphs=unet.use_graphs)
     return latents
+
+
+def write_image(latents, vae_path, png_path, dev, use_graphs=False):
+    """test/infer_xl.py:136-154: decode (the division by the scaling factor happens inside `decode_to_uint8`), denormalise,
+    round to 8 bits (the output convolution's epilogue) and save the first image."""
+    from leco_amd.vae import save_png
+    vae = model_util.load_vae(vae_path).to(dev)
+    vae.use_graphs = use_graphs
+    img = vae.decode_to_uint8(latents.float())
+    save_png(img[0], png_path)
+    vae.release()
+    print(f"image {img.shape[2]}x{img.shape[1]} -> {png_path}")
 
 
 if __name__ == "__main__":

@@ -228,7 +228,8 @@ int leco_layernorm_bwd(const void* x, int64_t ldx, const void* dy, int64_t lddy,
  * processor / xformers memory_efficient_attention (train_lora.py:68).  q/k/v/o are bf16 with
  * token stride ld* and batch stride bs* (elements); head h occupies columns [h*d, (h+1)*d).
  * lse: fp32 [batch][heads][sq] (log-sum-exp of the scaled scores), needed by the backward.
- * head_dim in {32, 40, 64, 80, 160}.
+ * head_dim in {32, 40, 64, 80, 160}; leco_attention_fwd alone also takes 128 and 512 (one wide head: the VAE decoder's
+ * mid-block attention), where lse may be NULL.  No score matrix exists in global memory at any sq / skv.
  * ---------------------------------------------------------------------- */
 int leco_attention_fwd(const void* q, int64_t ldq, int64_t bsq, const void* k, int64_t ldk,
                        int64_t bsk, const void* v, int64_t ldv, int64_t bsv, void* o, int64_t ldo,
@@ -266,6 +267,16 @@ int leco_conv_out(const void* x, const void* w, const float* bias, float* y, int
                   int32_t wd, int32_t c, int32_t cout, leco_stream_t stream);
 int leco_conv_out_bwd(const float* dy, const void* w, void* dx, int32_t batch, int32_t h, int32_t wd,
                       int32_t c, int32_t cout, leco_stream_t stream);
+/* VAE decoder entry (post_quant_conv of `decode`, with the division by the scaling factor folded in): a 1x1 convolution on
+ * the latents, y[b][o][p] = bias[o] + sum_c w[o][c] * (in_scale * x[b][c][p]); x fp32 NCHW (batch,cin,hw), w fp32 [cout][cin],
+ * y bf16 NCHW (batch,cout,hw) -- the input layout of leco_conv_in. */
+int leco_latent_affine(const float* x, const float* w, const float* bias, void* y, int32_t batch, int32_t hw, int32_t cin,
+                       int32_t cout, float in_scale, leco_stream_t stream);
+/* VAE decoder conv_out with the image epilogue: channels-last bf16 [batch*h*w][c] -> 3x3 pad 1, 3 outputs (RGB); w bf16
+ * [3][3][3][c], bias fp32 [3], c % 32 == 0.  Writes either or both (the other NULL) of y: fp32 NCHW (batch,3,h,w), the
+ * pre-rounding result, and img: uint8 NHWC (batch,h,w,3) = floor(clamp(y / 2 + 0.5, 0, 1) * 255 + 0.5). */
+int leco_conv_out_rgb(const void* x, const void* w, const float* bias, float* y, void* img, int32_t batch, int32_t h,
+                      int32_t wd, int32_t c, leco_stream_t stream);
 /* diffusers Timesteps(flip_sin_to_cos=True, freq_shift=0): out[i] = [cos | sin](t_i * f), bf16
  * [n][dim]; t_i = t_table[*idx + i*t_stride] (idx may be NULL => 0): the timestep is read on
  * the device so a captured graph can be replayed for every denoising step. */

@@ -218,6 +218,90 @@ def convert_open_clip(sd: Dict[str, torch.Tensor], prefix: str = "cond_stage_mod
     return out
 
 
+# ---- VAE decoder (`first_stage_model.*`) --------------------------------------------------------------------------------------
+VAE_PREFIX = "first_stage_model."
+_VAE_ATTN = {"norm": "group_norm", "q": "to_q", "k": "to_k", "v": "to_v", "proj_out": "to_out.0"}
+_VAE_ATTN_OLD = {"query": "to_q", "key": "to_k", "value": "to_v", "proj_attn": "to_out.0"}   # diffusers < 0.15 spelling
+
+
+def vae_decoder_levels(sd: Dict[str, torch.Tensor]) -> int:
+    """Number of resolution levels of the decoder in an LDM checkpoint (4 for the released VAEs)."""
+    idx = {int(m.group(1)) for k in sd for m in [re.match(re.escape(VAE_PREFIX) + r"decoder\.up\.(\d+)\.", k)] if m}
+    if not idx:
+        raise KeyError("no VAE decoder (first_stage_model.decoder.up.*) in the checkpoint")
+    return max(idx) + 1
+
+
+def _ldm_vae_key(k: str, levels: int) -> Optional[str]:
+    """One LDM decoder parameter name -> the diffusers name (None: not a decoder parameter: encoder, quant_conv, loss)."""
+    if k.startswith("post_quant_conv."):
+        return k
+    if not k.startswith("decoder."):
+        return None
+    k = k.replace(".nin_shortcut.", ".conv_shortcut.")
+    m = re.match(r"decoder\.mid\.block_(\d)\.(.+)", k)
+    if m:
+        return f"decoder.mid_block.resnets.{int(m.group(1)) - 1}.{m.group(2)}"
+    m = re.match(r"decoder\.mid\.attn_1\.(norm|q|k|v|proj_out)\.(weight|bias)", k)
+    if m:
+        return f"decoder.mid_block.attentions.0.{_VAE_ATTN[m.group(1)]}.{m.group(2)}"
+    m = re.match(r"decoder\.up\.(\d+)\.block\.(\d+)\.(.+)", k)
+    if m:
+        return f"decoder.up_blocks.{levels - 1 - int(m.group(1))}.resnets.{m.group(2)}.{m.group(3)}"
+    m = re.match(r"decoder\.up\.(\d+)\.upsample\.conv\.(.+)", k)
+    if m:
+        return f"decoder.up_blocks.{levels - 1 - int(m.group(1))}.upsamplers.0.conv.{m.group(2)}"
+    m = re.match(r"decoder\.norm_out\.(.+)", k)
+    if m:
+        return f"decoder.conv_norm_out.{m.group(1)}"
+    return k          # decoder.conv_in / decoder.conv_out keep their names; anything else surfaces as an unexpected key
+
+
+def convert_ldm_vae(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """`first_stage_model.*` entries of an LDM checkpoint -> diffusers-named state dict of the DECODER half
+    (post_quant_conv + decoder); the 1x1-conv attention weights [C][C][1][1] become Linear weights [C][C]."""
+    levels = vae_decoder_levels(sd)
+    out = {}
+    for k, v in sd.items():
+        if not k.startswith(VAE_PREFIX):
+            continue
+        nk = _ldm_vae_key(k[len(VAE_PREFIX):], levels)
+        if nk is None:
+            continue
+        if ".attentions.0.to_" in nk and nk.endswith(".weight") and v.ndim == 4:
+            v = v.reshape(v.shape[0], v.shape[1])
+        out[nk] = v
+    return out
+
+
+def normalise_vae_keys(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """A diffusers VAE state dict restricted to the decoder half, with the older attention spelling
+    (`query / key / value / proj_attn`) renamed to `to_q / to_k / to_v / to_out.0`."""
+    out = {}
+    for k, v in sd.items():
+        if not (k.startswith("decoder.") or k.startswith("post_quant_conv.")):
+            continue
+        m = re.match(r"(decoder\.mid_block\.attentions\.\d+)\.(query|key|value|proj_attn)\.(weight|bias)", k)
+        if m:
+            k = f"{m.group(1)}.{_VAE_ATTN_OLD[m.group(2)]}.{m.group(3)}"
+        if ".attentions." in k and ".to_" in k and k.endswith(".weight") and v.ndim == 4:
+            v = v.reshape(v.shape[0], v.shape[1])
+        out[k] = v
+    return out
+
+
+def detect_vae_config(sd: Dict[str, torch.Tensor], scaling_factor: Optional[float] = None):
+    """VAEConfig of a diffusers-named decoder state dict, from its tensor shapes.  The scaling factor is not stored in a
+    single-file checkpoint: 0.18215 (SD1.x / SD2.x) unless given."""
+    from .vae import VAEConfig
+    n_up = 1 + max(int(m.group(1)) for k in sd for m in [re.match(r"decoder\.up_blocks\.(\d+)\.", k)] if m)
+    rev = [int(sd[f"decoder.up_blocks.{i}.resnets.0.conv1.weight"].shape[0]) for i in range(n_up)]
+    layers = 1 + max(int(m.group(1)) for k in sd for m in [re.match(r"decoder\.up_blocks\.0\.resnets\.(\d+)\.", k)] if m)
+    return VAEConfig(latent_channels=int(sd["decoder.conv_in.weight"].shape[1]), out_channels=int(sd["decoder.conv_out.weight"].shape[0]),
+                     block_out_channels=tuple(reversed(rev)), layers_per_block=layers - 1,
+                     scaling_factor=0.18215 if scaling_factor is None else scaling_factor)
+
+
 def read_checkpoint(path: str) -> Dict[str, torch.Tensor]:
     if path.endswith(".safetensors"):
         from safetensors.torch import load_file

@@ -1,6 +1,7 @@
 // Flash-style attention forward for the UNet's self- and cross-attention:
 //   O = softmax(Q K^T * scale) V  per (batch, head), never materialising the score matrix.
-// Head dims 32/40/64/80/160 (SD1.x: 40/80/160, SD2.x/SDXL: 64), key counts 77 .. 9216.
+// Head dims 32/40/64/80/160 (SD1.x: 40/80/160, SD2.x/SDXL: 64), key counts 77 .. 9216; forward only: 128 / 512 (the VAE
+// decoder's single wide head, attn_fwd_wide_kernel below).
 //
 // gfx950 mapping (wave64, v_mfma_f32_16x16x32_bf16):
 //   * one workgroup = 4 waves = QF*64 query rows of one (b, head); K/V stream through LDS in
@@ -889,6 +890,193 @@ int launch_bwd(const AttnBwdArgs& a, int batch, hipStream_t s) {
     return check_launch("leco_attention_bwd");
 }
 
+// ------------------------------------------------------------------------------------------
+// Wide-head forward (the VAE decoder's mid-block attention: ONE head as wide as the channel count, d = 512; d = 128 for the
+// tiny synthetic decoder).  Forward only, flash-style: O(S d) memory at any S.  A wave cannot hold 16 query rows x d of O
+// next to a d-wide Q fragment (d = 512: 64 + 512 registers), so the two products are split differently over the 4 waves of
+// a workgroup (64 query rows):
+//   phase A  wave w owns the query stripe 16 w .. 16 w + 15 over the FULL d (Q fragment in registers, d / 8 VGPRs): S^T = K Q^T
+//            against the 64-key K tile in LDS, online softmax per lane-owned row exactly as in attn_fwd_kernel; the bf16 P^T
+//            operand registers and the row's rescale factor alpha go to LDS;
+//   phase B  wave w owns the COLUMN slice d / 4 * w .. of O for all 64 query rows (fp32, 64 x d / 4: d / 4 VGPRs): it reads the
+//            four stripes' P^T operands back lane-for-lane (the layout a lane wrote is the layout a lane needs) and
+//            O^T += V^T P^T against the V tile in LDS through the transpose read.
+// LDS: K tile 64 x (d + 8), V tile 64 x (d + 16), P 8 KB: 140 KB at d = 512 -- one workgroup per CU, single-buffered (three
+// barriers per tile).  The kernel runs once per decode.
+template <int D>
+struct AttnWideCfg {
+    static constexpr int DW = D / 4, NKS = D / 32, NFD = DW / 16, NDC = D / 8;
+    static constexpr int KROW = D + 8;
+    static constexpr int VRB0 = D * 2, VRB = ((VRB0 / 32) % 2) ? VRB0 : VRB0 + 32, VROW = VRB / 2;
+    static constexpr int OFF_V = KT * KROW * 2, OFF_P = OFF_V + KT * VROW * 2, OFF_A = OFF_P + 8 * 64 * 16;
+    static constexpr int LDS_BYTES = OFF_A + 64 * 4;
+    static_assert(D % 64 == 0 && (KT * NDC) % 256 == 0, "wide attention: d must be a multiple of 64");
+    static_assert(LDS_BYTES <= 160 * 1024, "wide attention: tiles exceed the 160 KB LDS");
+};
+
+template <int D>
+__global__ __launch_bounds__(256) LECO_MIN_WAVES_PER_SIMD(1) void attn_fwd_wide_kernel(AttnArgs p) {
+    using Cf = AttnWideCfg<D>;
+    constexpr int DW = Cf::DW, NKS = Cf::NKS, NFD = Cf::NFD, NDC = Cf::NDC, KROW = Cf::KROW, VROW = Cf::VROW;
+    unsigned char* lds = dyn_lds();
+    bf16_t* sK = (bf16_t*)lds;
+    bf16_t* sV = (bf16_t*)(lds + Cf::OFF_V);
+    u32x4* sP = (u32x4*)(lds + Cf::OFF_P);     // [stripe 4][s 2][lane 64]: the P^T operand registers of each stripe's wave
+    float* sA = (float*)(lds + Cf::OFF_A);     // [64 query rows]: alpha of the tile (after the last tile: the row sum l)
+
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int fr = lane & 15, fg = lane >> 4;
+    int bx, h, b;
+    attn_ids(p.xcd_remap, bx, h, b);
+    const int q0 = bx * 64;
+    const bf16_t* qb = p.q + (int64_t)b * p.bsq + (int64_t)h * D;
+    const bf16_t* kb = p.k + (int64_t)b * p.bsk + (int64_t)h * D;
+    const bf16_t* vb = p.v + (int64_t)b * p.bsv + (int64_t)h * D;
+
+    const u32x4 zero4 = {0u, 0u, 0u, 0u};
+    bf16x8 qf[NKS];
+    {
+        const int qrow = q0 + wave * 16 + fr;
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) {
+            u32x4 t = qrow < p.sq ? *(const u32x4*)(qb + (int64_t)qrow * p.ldq + (ks * 4 + fg) * 8) : zero4;
+            qf[ks] = __builtin_bit_cast(bf16x8, t);
+        }
+    }
+    f32x4 acc_o[4][NFD];
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int fd = 0; fd < NFD; ++fd) acc_o[u][fd] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float m_run = -INFINITY, l_run = 0.f;
+
+    for (int kv0 = 0; kv0 < p.skv; kv0 += KT) {
+        // stage the K and V tiles (rows past skv: zeros); thread e -> (key = e / NDC, 16-byte chunk e % NDC)
+#pragma unroll 4
+        for (int e = tid; e < KT * NDC; e += 256) {
+            const int key = e / NDC, ch = e - key * NDC;
+            const bool ok = kv0 + key < p.skv;
+            const u32x4 tk = ok ? *(const u32x4*)(kb + (int64_t)(kv0 + key) * p.ldk + ch * 8) : zero4;
+            const u32x4 tv = ok ? *(const u32x4*)(vb + (int64_t)(kv0 + key) * p.ldv + ch * 8) : zero4;
+            *(u32x4*)(sK + key * KROW + ch * 8) = tk;
+            *(u32x4*)(sV + key * VROW + ch * 8) = tv;
+        }
+        __syncthreads();
+
+        // ---- phase A: S^T = K Q^T for this wave's stripe: lane holds S[q = fr][key = kv0 + 16 f + 4 fg + r]
+        f32x4 acc_s[4];
+#pragma unroll
+        for (int f = 0; f < 4; ++f) {
+            f32x4 a = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < NKS; ++ks) {
+                const bf16x8 kf = *(const bf16x8*)(sK + (16 * f + fr) * KROW + (ks * 4 + fg) * 8);
+                a = mfma16(kf, qf[ks], a);
+            }
+            acc_s[f] = a;
+        }
+        float mx = -INFINITY;
+#pragma unroll
+        for (int f = 0; f < 4; ++f)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int key = kv0 + 16 * f + 4 * fg + r;
+                acc_s[f][r] = key < p.skv ? acc_s[f][r] : -INFINITY;
+                mx = fmaxf(mx, acc_s[f][r]);
+            }
+        mx = rows4_max(mx);
+        const float m_new = fmaxf(m_run, mx * p.scale_log2);     // scale > 0: max and scale commute
+        const float alpha = fast_exp2(m_run - m_new);
+        m_run = m_new;
+        float rs = 0.f;
+        u32x4 pw[2];
+#pragma unroll
+        for (int f = 0; f < 4; ++f) {
+            const float e0 = fast_exp2(fmaf(acc_s[f][0], p.scale_log2, -m_new));
+            const float e1 = fast_exp2(fmaf(acc_s[f][1], p.scale_log2, -m_new));
+            const float e2 = fast_exp2(fmaf(acc_s[f][2], p.scale_log2, -m_new));
+            const float e3 = fast_exp2(fmaf(acc_s[f][3], p.scale_log2, -m_new));
+            rs += (e0 + e1) + (e2 + e3);
+            pw[f >> 1][(f & 1) * 2] = pack_bf2(e0, e1);
+            pw[f >> 1][(f & 1) * 2 + 1] = pack_bf2(e2, e3);
+        }
+        l_run = l_run * alpha + rs;
+        sP[(wave * 2 + 0) * 64 + lane] = pw[0];
+        sP[(wave * 2 + 1) * 64 + lane] = pw[1];
+        if (fg == 0) sA[wave * 16 + fr] = alpha;
+        __syncthreads();
+
+        // ---- phase B: O^T[d slice of this wave][all 64 rows] += V^T P^T (key order of the P^T registers: MFMA k index
+        // 8 fg + t <-> tile key 16 (2 s + (t >> 2)) + 4 fg + (t & 3), matched by the transpose reads as in attn_fwd_kernel)
+        float al[4];
+        bf16x8 pf[4][2];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            al[u] = sA[16 * u + fr];
+            pf[u][0] = __builtin_bit_cast(bf16x8, sP[(u * 2 + 0) * 64 + lane]);
+            pf[u][1] = __builtin_bit_cast(bf16x8, sP[(u * 2 + 1) * 64 + lane]);
+        }
+#pragma unroll
+        for (int fd = 0; fd < NFD; ++fd) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                acc_o[u][fd][0] *= al[u]; acc_o[u][fd][1] *= al[u];
+                acc_o[u][fd][2] *= al[u]; acc_o[u][fd][3] *= al[u];
+            }
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const bf16_t* blk = sV + (16 * (2 * s) + 4 * fg + (fr >> 2)) * VROW + wave * DW + 16 * fd + 4 * (fr & 3);
+                const u32x2 lo = lds_read_tr16(blk);
+                const u32x2 hi = lds_read_tr16(blk + 16 * VROW);
+                const u32x4 t = {lo[0], lo[1], hi[0], hi[1]};
+                const bf16x8 vf = __builtin_bit_cast(bf16x8, t);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) acc_o[u][fd] = mfma16(vf, pf[u][s], acc_o[u][fd]);
+            }
+        }
+        __syncthreads();      // every wave is done with K, V, P and alpha of this tile
+    }
+
+    // row sums of the four stripes -> LDS; each wave normalises and stores its column slice of all 64 rows
+    {
+        const float l = rows4_sum(l_run);
+        const int qrow = q0 + wave * 16 + fr;
+        if (fg == 0) {
+            sA[wave * 16 + fr] = l;
+            if (p.lse && qrow < p.sq) p.lse[((int64_t)b * p.heads + h) * p.sq + qrow] = (m_run + log2f(l)) * 0.6931471805599453f;
+        }
+    }
+    __syncthreads();
+    bf16_t* ob = p.o + (int64_t)b * p.bso + (int64_t)h * D + wave * DW;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const float inv = 1.f / sA[16 * u + fr];
+        const int qrow = q0 + 16 * u + fr;
+        if (qrow < p.sq) {
+#pragma unroll
+            for (int fd = 0; fd < NFD; ++fd) {
+                const f32x4 o = acc_o[u][fd];
+                const u32x2 w = {pack_bf2(o[0] * inv, o[1] * inv), pack_bf2(o[2] * inv, o[3] * inv)};
+                *(u32x2*)(ob + (int64_t)qrow * p.ldo + 16 * fd + 4 * fg) = w;
+            }
+        }
+    }
+}
+template <int D>
+int launch_fwd_wide(const AttnArgs& a, int batch, hipStream_t s) {
+    using Cf = AttnWideCfg<D>;
+    static bool attr_set[64] = {};
+    int dev_id = 0;
+    (void)hipGetDevice(&dev_id);
+    if (Cf::LDS_BYTES > 64 * 1024 && (dev_id < 0 || dev_id >= 64 || !attr_set[dev_id])) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_wide_kernel<D>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, Cf::LDS_BYTES);
+        if (dev_id >= 0 && dev_id < 64) attr_set[dev_id] = true;
+    }
+    hipLaunchKernelGGL((attn_fwd_wide_kernel<D>), dim3(cdiv(a.sq, 64), a.heads, batch), dim3(256), Cf::LDS_BYTES, s, a);
+    return check_launch("leco_attention_fwd");
+}
+
 template <int D>
 int launch_fwd(const AttnArgs& a, int batch, hipStream_t s) {
     static const int force_qf = [] {   // tuning override: LECO_ATTN_QF = 1 | 2 (query fragments per wave)
@@ -950,7 +1138,9 @@ extern "C" int leco_attention_fwd(const void* q, int64_t ldq, int64_t bsq, const
         case 64: return launch_fwd<64>(a, batch, s);
         case 80: return launch_fwd<80>(a, batch, s);
         case 160: return launch_fwd<160>(a, batch, s);
-        default: return fail(-EINVAL, "attention: unsupported head_dim %d (32/40/64/80/160)", head_dim);
+        case 128: return launch_fwd_wide<128>(a, batch, s);      // single wide head (VAE mid-block): forward only, lse optional
+        case 512: return launch_fwd_wide<512>(a, batch, s);
+        default: return fail(-EINVAL, "attention: unsupported head_dim %d (32/40/64/80/160, forward only: 128/512)", head_dim);
     }
 }
 

@@ -324,6 +324,74 @@ __global__ __launch_bounds__(256) void conv_out_mfma_kernel(const bf16_t* x, con
     }
 }
 
+// ---- VAE decoder entry: post_quant_conv (a 1x1 convolution on the latents) with the 1 / scaling_factor of `decode` folded in:
+// y[b][o][p] = bias[o] + sum_c w[o][c] * (in_scale * x[b][c][p]); fp32 NCHW in, bf16 NCHW out (what conv_in reads).
+__global__ __launch_bounds__(256) void latent_affine_kernel(const float* x, const float* w, const float* bias, bf16_t* y, int B,
+                                                             int HW, int Cin, int Cout, float in_scale) {
+    const int64_t total = (int64_t)B * Cout * HW;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+        const int64_t bo = e / HW;
+        const int p = (int)(e - bo * HW), o = (int)(bo % Cout), b = (int)(bo / Cout);
+        float acc = bias ? bias[o] : 0.f;
+        for (int c = 0; c < Cin; ++c) acc += w[o * Cin + c] * (in_scale * x[((int64_t)b * Cin + c) * HW + p]);
+        y[e] = f2bf(acc);
+    }
+}
+
+// ---- VAE decoder conv_out: 3x3 pad 1, C -> 3 (RGB), channels-last bf16 in, with the image epilogue --------------------------
+// Same mapping as conv_out_mfma_kernel (16 pixels per workgroup, the 27 C / 32 k-steps split over the 4 waves in units of
+// (channel block, kernel row), partial sums meet in LDS).  Outputs, either or both: y fp32 NCHW (batch, 3, h, w) -- the
+// pre-rounding result -- and img uint8 NHWC (batch, h, w, 3) = floor(clamp(y / 2 + 0.5, 0, 1) * 255 + 0.5): the
+// denormalisation of the sampling scripts followed by the rounding of an 8-bit image writer.
+__global__ __launch_bounds__(256) void conv_out_rgb_kernel(const bf16_t* x, const bf16_t* w, const float* bias, float* y,
+                                                            unsigned char* img, int B, int H, int W, int C) {
+    constexpr int COUT = 3;
+    __shared__ f32x4 red[4][64];
+    const int lane = lane_id(), wave = uniform((int)(threadIdx.x >> 6)), fr = lane & 15, fg = lane >> 4;
+    const int npix = B * H * W, pix = (int)blockIdx.x * 16 + fr;       // (host: < 2^30; 32-bit divisions only)
+    const bool pv = pix < npix;
+    const unsigned pp = pv ? (unsigned)pix : 0u;
+    const unsigned row = pp / (unsigned)W;
+    const int px = (int)(pp - row * (unsigned)W), b = (int)(row / (unsigned)H), py = (int)(row - (unsigned)b * (unsigned)H);
+    const int nkc = C / 32;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    const u32x4 z = {0u, 0u, 0u, 0u};
+    constexpr int UU = 4;                                  // units (x 3 taps) in flight per wave
+    const int nunits = 3 * nkc;
+    for (int u0 = wave; u0 < nunits; u0 += 4 * UU) {
+        u32x4 xv[UU][3], wv[UU][3];
+#pragma unroll
+        for (int uu = 0; uu < UU; ++uu) {
+            const int unit = u0 + 4 * uu;
+            const int cb = unit / 3, ky = unit - 3 * cb;
+            const int iy = py + ky - 1;
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx) {
+                const int ix = px + kx - 1;
+                const bool ok = unit < nunits && pv && iy >= 0 && iy < H && ix >= 0 && ix < W;
+                xv[uu][kx] = ok ? *(const u32x4*)(x + ((int64_t)(b * H + iy) * W + ix) * C + cb * 32 + fg * 8) : z;
+                wv[uu][kx] = (unit < nunits && fr < COUT) ? *(const u32x4*)(w + (int64_t)(fr * 9 + ky * 3 + kx) * C + cb * 32 + fg * 8) : z;
+            }
+        }
+#pragma unroll
+        for (int uu = 0; uu < UU; ++uu)
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx)
+                acc = mfma16(__builtin_bit_cast(bf16x8, wv[uu][kx]), __builtin_bit_cast(bf16x8, xv[uu][kx]), acc);
+    }
+    red[wave][lane] = acc;
+    __syncthreads();
+    if (wave == 0 && fg == 0 && pv) {                      // rows n = 0..2 of column (pixel) fr live in the lanes fg = 0
+        const f32x4 a0 = red[0][lane], a1 = red[1][lane], a2 = red[2][lane], a3 = red[3][lane];
+#pragma unroll
+        for (int n = 0; n < COUT; ++n) {
+            const float v = (a0[n] + a1[n]) + (a2[n] + a3[n]) + bias[n];
+            if (y) y[((int64_t)(b * COUT + n) * H + py) * W + px] = v;
+            if (img) img[(int64_t)pix * COUT + n] = (unsigned char)floorf(fminf(fmaxf(v * 0.5f + 0.5f, 0.f), 1.f) * 255.f + 0.5f);
+        }
+    }
+}
+
 // dgrad of conv_out: dx[pix][c] = sum_{tap,o} dy[b][o][pix - off(tap)] * w[o][tap][c]
 template <int COUT>
 __global__ __launch_bounds__(256) void conv_out_bwd_kernel(const float* dy, const bf16_t* w, bf16_t* dx, int B,
@@ -923,6 +991,23 @@ extern "C" int leco_conv_out(const void* x, const void* w, const float* bias, fl
     hipLaunchKernelGGL((conv_out_kernel<4>), dim3((unsigned)((npix + 3) / 4)), dim3(256), 0, LECO_STREAM,
                        (const bf16_t*)x, (const bf16_t*)w, bias, y, batch, h, wd, c);
     return check_launch("leco_conv_out");
+}
+extern "C" int leco_latent_affine(const float* x, const float* w, const float* bias, void* y, int32_t batch, int32_t hw,
+                                  int32_t cin, int32_t cout, float in_scale, leco_stream_t stream) {
+    if (batch <= 0 || hw <= 0 || cin <= 0 || cout <= 0) return fail(-EINVAL, "latent_affine: empty problem");
+    hipLaunchKernelGGL(latent_affine_kernel, dim3(grid_for((int64_t)batch * cout * hw)), dim3(256), 0, LECO_STREAM, x, w, bias,
+                       (bf16_t*)y, batch, hw, cin, cout, in_scale);
+    return check_launch("leco_latent_affine");
+}
+extern "C" int leco_conv_out_rgb(const void* x, const void* w, const float* bias, float* y, void* img, int32_t batch, int32_t h,
+                                 int32_t wd, int32_t c, leco_stream_t stream) {
+    if (c % 32) return fail(-EINVAL, "conv_out_rgb: C=%d %% 32 != 0", c);
+    if (!y && !img) return fail(-EINVAL, "conv_out_rgb: neither y nor img given");
+    const int64_t npix = (int64_t)batch * h * wd;
+    if (batch <= 0 || h <= 0 || wd <= 0 || npix >= (1ll << 30)) return fail(-EINVAL, "conv_out_rgb: batch * h * w out of range");
+    hipLaunchKernelGGL(conv_out_rgb_kernel, dim3((unsigned)((npix + 15) / 16)), dim3(256), 0, LECO_STREAM,
+                       (const bf16_t*)x, (const bf16_t*)w, bias, y, (unsigned char*)img, batch, h, wd, c);
+    return check_launch("leco_conv_out_rgb");
 }
 extern "C" int leco_conv_out_bwd(const float* dy, const void* w, void* dx, int32_t batch, int32_t h, int32_t wd,
                                  int32_t c, int32_t cout, leco_stream_t stream) {

@@ -229,6 +229,62 @@ def load_synthetic_model(kind: str, seed: int = 1234):
     return SyntheticTokenizer(), SyntheticTextEncoder(cfg.cross_attention_dim), unet
 
 
+def _load_state_into_vae(vae, sd, what: str):
+    missing, unexpected = vae.load_state_dict(sd, strict=False)
+    if missing:
+        raise KeyError(f"{what}: the VAE decoder lacks {missing[0]!r}" + (f" (and {len(missing) - 1} more)" if len(missing) > 1 else ""))
+    if unexpected:
+        raise KeyError(f"{what}: unexpected VAE decoder key {unexpected[0]!r}"
+                       + (f" (and {len(unexpected) - 1} more)" if len(unexpected) > 1 else ""))
+    return vae
+
+
+SYNTHETIC_VAE = {"sd15": 0.18215, "sd21": 0.18215, "sdxl": 0.13025}      # real decoder shape, scaling factor
+
+
+def load_vae(path: str, precision: str = "bfloat16", scaling_factor: Optional[float] = None):
+    """The VAE decoder (`leco_amd.vae.AutoencoderKL`) of
+
+    * a diffusers pipeline folder (its ``vae/`` subfolder) or the ``vae`` folder itself: ``config.json`` +
+      ``diffusion_pytorch_model.safetensors`` / ``.bin``; both attention spellings (``to_q`` ... / ``query`` ...);
+    * a single-file LDM checkpoint (``first_stage_model.*``; encoder and ``quant_conv`` are ignored);
+    * ``synthetic:<sd15|sd21|sdxl>`` (the real decoder shape, seeded random weights) / ``synthetic:<tiny|tiny_xl>``.
+
+    A missing or unexpected decoder key is an error naming it.  The decoder computes in bfloat16 only."""
+    from . import ckpt_convert as cc
+    from . import vae as V
+    if precision not in ("bfloat16", "bf16", torch.bfloat16):
+        raise NotImplementedError(f"load_vae: compute precision {precision!r} is not implemented for the VAE decoder (bfloat16 only)")
+    p = path
+    if p.startswith("synthetic:"):
+        kind = p.split(":", 1)[1]
+        if kind in SYNTHETIC_VAE:
+            cfg = V.VAEConfig(scaling_factor=SYNTHETIC_VAE[kind])
+        elif kind in ("tiny", "tiny_xl", "tinyxl"):
+            cfg = V.tiny_vae_config(0.18215 if kind == "tiny" else 0.13025)
+        else:
+            raise ValueError(f"{p}: unknown synthetic VAE (sd15 | sd21 | sdxl | tiny | tiny_xl)")
+        return V.init_synthetic_vae_(V.AutoencoderKL(cfg))
+    if os.path.isdir(p):
+        d = os.path.join(p, "vae") if os.path.isfile(os.path.join(p, "vae", "config.json")) else p
+        if not os.path.isfile(os.path.join(d, "config.json")):
+            raise FileNotFoundError(f"{p}: no vae/config.json or config.json")
+        cfg = V.VAEConfig.from_json(os.path.join(d, "config.json"))
+        if scaling_factor is not None:
+            cfg.scaling_factor = scaling_factor
+        st = os.path.join(d, "diffusion_pytorch_model.safetensors")
+        if os.path.exists(st):
+            from safetensors.torch import load_file
+            sd = load_file(st)
+        else:
+            sd = torch.load(os.path.join(d, "diffusion_pytorch_model.bin"), map_location="cpu")
+        return _load_state_into_vae(V.AutoencoderKL(cfg), cc.normalise_vae_keys(sd), d)
+    if p.endswith(".ckpt") or p.endswith(".safetensors"):
+        sd = cc.convert_ldm_vae(cc.read_checkpoint(p))
+        return _load_state_into_vae(V.AutoencoderKL(cc.detect_vae_config(sd, scaling_factor)), sd, p)
+    raise FileNotFoundError(f"{p}: not a local diffusers folder, single-file checkpoint or synthetic:<sd15|sd21|sdxl|tiny|tiny_xl>")
+
+
 def load_models(pretrained_model_name_or_path: str, scheduler_name: str, v2: bool = False, v_pred: bool = False,
                 weight_dtype: torch.dtype = torch.float32):
     p = pretrained_model_name_or_path

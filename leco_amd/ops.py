@@ -37,6 +37,8 @@ _SIGS = {
     "leco_conv_in": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
     "leco_conv_out": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
     "leco_conv_out_bwd": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
+    "leco_latent_affine": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp],
+    "leco_conv_out_rgb": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
     "leco_timestep_embedding": [_vp, _vp, _i32, _i32, _i32, _vp, _vp],
     "leco_advance": [_vp, _vp],
     "leco_cfg_ddim_step": [_vp, _vp, _vp, _vp, _vp, _f32, _i64, _vp],
@@ -247,6 +249,16 @@ def conv_in(x, w, bias, y, batch, h, wd, cin, cout) -> Op:
 
 def conv_out(x, w, bias, y, batch, h, wd, c, cout) -> Op:
     return Op("leco_conv_out", (ptr(x), ptr(w), ptr(bias), ptr(y), batch, h, wd, c, cout))
+
+
+def latent_affine(x, w, bias, y, batch, hw, cin, cout, in_scale) -> Op:
+    """y (bf16 NCHW) = 1x1 conv of in_scale * x (fp32 NCHW): the VAE's post_quant_conv on latents / scaling_factor."""
+    return Op("leco_latent_affine", (ptr(x), ptr(w), ptr(bias), ptr(y), batch, hw, cin, cout, float(in_scale)), keep=(x, w, bias, y))
+
+
+def conv_out_rgb(x, w, bias, y, img, batch, h, wd, c) -> Op:
+    """3x3 conv to RGB: ``y`` fp32 NCHW and / or ``img`` uint8 NHWC (either may be None), see include/leco_hip.h."""
+    return Op("leco_conv_out_rgb", (ptr(x), ptr(w), ptr(bias), ptr(y), ptr(img), batch, h, wd, c), keep=(x, w, bias, y, img))
 
 
 def conv_out_bwd(dy, w, dx, batch, h, wd, c, cout) -> Op:

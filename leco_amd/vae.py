@@ -1,0 +1,464 @@
+"""The decoder half of the Stable Diffusion VAE (diffusers 0.20 ``AutoencoderKL`` / ``Decoder``) on the HIP kernels:
+latents -> image, what the reference's ``test/infer_xl.py:136-154`` does with ``vae.decode`` + ``save_image``.
+
+The module tree only HOLDS weights under the diffusers parameter names (``post_quant_conv``, ``decoder.conv_in``,
+``decoder.mid_block.resnets.N``, ``decoder.mid_block.attentions.0.{group_norm,to_q,to_k,to_v,to_out.0}``,
+``decoder.up_blocks.N.resnets.M``, ``decoder.up_blocks.N.upsamplers.0.conv``, ``decoder.conv_norm_out``,
+``decoder.conv_out``), so a diffusers state dict loads as is.  ``decode`` runs a forward-only launch plan built from
+``ops.*`` per (batch, h, w): bf16 activations, fp32 accumulation, channels-last; replayed from a hipGraph when
+``use_graphs`` is set.
+
+    post_quant_conv (1 / scaling_factor folded in)      leco_latent_affine
+    conv_in                                             leco_conv_in
+    resnet: GN+SiLU -> conv3x3 -> GN+SiLU -> conv3x3 (+ shortcut as the GEMM's residual operand)
+    mid attention: GN -> fused q|k|v Linear -> one head of width C (leco_attention_fwd, d = C) -> out Linear + residual
+    upsample: nearest 2x folded into the conv's operand gather (LECO_A_CONV3_UP2)
+    conv_norm_out + SiLU -> conv_out -> fp32 NCHW and / or 8-bit NHWC pixels (leco_conv_out_rgb)
+"""
+from __future__ import annotations
+
+import ctypes as C
+import json
+import struct
+import zlib
+from dataclasses import dataclass, fields
+from typing import Dict, List, Optional, Tuple
+
+import torch
+from torch import nn
+
+from . import hip, ops
+from .hip import ACT_NONE, ACT_SILU, A_CONV3_S1, A_CONV3_UP2, A_PLAIN, gemm_args
+
+bf16 = torch.bfloat16
+GN_EPS = 1e-6
+WIDE_HEAD_DIMS = (128, 512)      # head widths leco_attention_fwd has a single-head kernel for
+
+
+@dataclass
+class VAEConfig:
+    latent_channels: int = 4
+    out_channels: int = 3
+    block_out_channels: Tuple[int, ...] = (128, 256, 512, 512)
+    layers_per_block: int = 2
+    norm_num_groups: int = 32
+    scaling_factor: float = 0.18215
+
+    @classmethod
+    def from_dict(cls, d: dict) -> "VAEConfig":
+        known = {f.name for f in fields(cls)}
+        kw = {k: v for k, v in d.items() if k in known}
+        if "block_out_channels" in kw:
+            kw["block_out_channels"] = tuple(kw["block_out_channels"])
+        return cls(**kw)
+
+    @classmethod
+    def from_json(cls, path: str) -> "VAEConfig":
+        with open(path) as f:
+            return cls.from_dict(json.load(f))
+
+
+def sd_vae_config() -> VAEConfig:
+    return VAEConfig()
+
+
+def sdxl_vae_config() -> VAEConfig:
+    return VAEConfig(scaling_factor=0.13025)
+
+
+def tiny_vae_config(scaling_factor: float = 0.18215) -> VAEConfig:
+    """Four levels (the 8x factor holds), small enough for the host emulator."""
+    return VAEConfig(block_out_channels=(64, 64, 128, 128), layers_per_block=1, scaling_factor=scaling_factor)
+
+
+# ---- weight holders (diffusers names) ------------------------------------------------------------------------------------------
+class ResnetBlock2D(nn.Module):
+    def __init__(self, cin: int, cout: int, groups: int):
+        super().__init__()
+        self.in_channels, self.out_channels = cin, cout
+        self.norm1 = nn.GroupNorm(groups, cin, eps=GN_EPS)
+        self.conv1 = nn.Conv2d(cin, cout, 3, 1, 1)
+        self.norm2 = nn.GroupNorm(groups, cout, eps=GN_EPS)
+        self.conv2 = nn.Conv2d(cout, cout, 3, 1, 1)
+        self.conv_shortcut = nn.Conv2d(cin, cout, 1) if cin != cout else None
+
+
+class Attention(nn.Module):
+    def __init__(self, c: int, groups: int):
+        super().__init__()
+        self.group_norm = nn.GroupNorm(groups, c, eps=GN_EPS)
+        self.to_q, self.to_k, self.to_v = nn.Linear(c, c), nn.Linear(c, c), nn.Linear(c, c)
+        self.to_out = nn.ModuleList([nn.Linear(c, c)])
+
+
+class UNetMidBlock2D(nn.Module):
+    def __init__(self, c: int, groups: int):
+        super().__init__()
+        self.resnets = nn.ModuleList([ResnetBlock2D(c, c, groups), ResnetBlock2D(c, c, groups)])
+        self.attentions = nn.ModuleList([Attention(c, groups)])
+
+
+class Upsample2D(nn.Module):
+    def __init__(self, c: int):
+        super().__init__()
+        self.conv = nn.Conv2d(c, c, 3, 1, 1)
+
+
+class UpDecoderBlock2D(nn.Module):
+    def __init__(self, cin: int, cout: int, layers: int, groups: int, upsample: bool):
+        super().__init__()
+        self.resnets = nn.ModuleList([ResnetBlock2D(cin if i == 0 else cout, cout, groups) for i in range(layers)])
+        if upsample:
+            self.upsamplers = nn.ModuleList([Upsample2D(cout)])
+        else:
+            self.upsamplers = None
+
+
+class Decoder(nn.Module):
+    def __init__(self, cfg: VAEConfig):
+        super().__init__()
+        ch, g = cfg.block_out_channels, cfg.norm_num_groups
+        self.conv_in = nn.Conv2d(cfg.latent_channels, ch[-1], 3, 1, 1)
+        self.mid_block = UNetMidBlock2D(ch[-1], g)
+        rev = list(reversed(ch))
+        self.up_blocks = nn.ModuleList()
+        cout = rev[0]
+        for i, c in enumerate(rev):
+            cin, cout = cout, c
+            self.up_blocks.append(UpDecoderBlock2D(cin, cout, cfg.layers_per_block + 1, g, i != len(rev) - 1))
+        self.conv_norm_out = nn.GroupNorm(g, ch[0], eps=GN_EPS)
+        self.conv_out = nn.Conv2d(ch[0], cfg.out_channels, 3, 1, 1)
+
+
+class DecoderOutput:
+    def __init__(self, sample: torch.Tensor):
+        self.sample = sample
+
+
+# ---- launch plan ---------------------------------------------------------------------------------------------------------------
+class _Pool:
+    """Activation buffers of one plan.  The launches of a plan are stream-ordered, so a buffer whose last reader has been
+    appended can be handed to the next producer: `take` returns the smallest free block that fits (else a new one),
+    `give` returns a block.  Together with the build order of `_Builder` the tensors ping-pong between a few blocks."""
+
+    def __init__(self, device):
+        self.device = device
+        self.free: List[torch.Tensor] = []
+        self.all: List[torch.Tensor] = []
+
+    def take(self, nbytes: int) -> torch.Tensor:
+        fit = [b for b in self.free if b.numel() >= nbytes]
+        if fit:
+            b = min(fit, key=lambda t: t.numel())
+            self.free = [t for t in self.free if t is not b]
+            return b
+        b = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.all.append(b)
+        return b
+
+    def give(self, b: torch.Tensor) -> None:
+        self.free.append(b)
+
+    def nbytes(self) -> int:
+        return sum(b.numel() for b in self.all)
+
+
+class _Act:
+    """A channels-last bf16 activation [rows][cols] living in a pool block."""
+    __slots__ = ("blk", "rows", "cols")
+
+    def __init__(self, blk, rows, cols):
+        self.blk, self.rows, self.cols = blk, rows, cols
+
+    @property
+    def ptr(self) -> int:
+        return self.blk.data_ptr()
+
+
+class VAEPlan:
+    def __init__(self):
+        self.ops: List[ops.Op] = []
+        self.graph = None
+        self.x_in: torch.Tensor = None       # fp32 (B, latent_channels, h, w): unscaled latents
+        self.sample: torch.Tensor = None     # fp32 (B, 3, 8h, 8w)
+        self.image: torch.Tensor = None      # uint8 (B, 8h, 8w, 3)
+        self.pool: _Pool = None
+        self.stats: torch.Tensor = None
+
+
+class _Builder:
+    """Forward-only plan of one (batch, h, w): its own small builder (no LoRA, no time embedding, no backward tape)."""
+
+    def __init__(self, eng: "VAEEngine", B: int, h: int, w: int):
+        self.eng, self.B, self.h, self.w = eng, B, h, w
+        self.plan = VAEPlan()
+        self.pool = self.plan.pool = _Pool(eng.device)
+        self.out = self.plan.ops
+        G = eng.cfg.norm_num_groups
+        # GroupNorm statistics scratch, shared by every norm of the plan (the launches are ordered); the plan owns it
+        self.stats = self.plan.stats = torch.zeros(B * G * 2 * 257, dtype=torch.float32, device=eng.device)
+
+    def act(self, rows: int, cols: int) -> _Act:
+        return _Act(self.pool.take(rows * cols * 2), rows, cols)
+
+    def drop(self, a: _Act) -> None:
+        self.pool.give(a.blk)
+
+    def groupnorm(self, name: str, x: _Act, hw: int, act: int) -> _Act:
+        gamma, beta = self.eng.norm_p[name]
+        y = self.act(x.rows, x.cols)
+        self.out.append(ops.groupnorm_fwd(x.ptr, x.cols, None, 0, 0, gamma, beta, self.B, hw, x.cols, self.eng.cfg.norm_num_groups,
+                                          GN_EPS, act, self.stats, y.ptr, y.cols))
+        return y
+
+    def gemm(self, name: str, x: _Act, rows: int, *, conv=None, amode=A_PLAIN, residual: Optional[_Act] = None) -> _Act:
+        w, bias = self.eng.gemm_w[name]
+        n, k = w.shape
+        y = self.act(rows, n)
+        g = gemm_args(x.ptr, w, y.ptr, m=rows, n=n, k=k, lda=x.cols, a_mode=amode, conv=conv, bias=bias,
+                      residual=None if residual is None else residual.ptr, ldr=0 if residual is None else residual.cols, ldc=n)
+        self.out.append(ops.gemm(g, keep=(w, bias, x.blk, y.blk, None if residual is None else residual.blk), ws=self.eng.workspace))
+        return y
+
+    def resnet(self, name: str, x: _Act, hs: int, ws: int) -> _Act:
+        hw, rows, conv = hs * ws, self.B * hs * ws, (self.B, hs, ws, hs, ws)
+        n1 = self.groupnorm(name + ".norm1", x, hw, ACT_SILU)
+        h1 = self.gemm(name + ".conv1", n1, rows, conv=conv, amode=A_CONV3_S1)
+        self.drop(n1)
+        n2 = self.groupnorm(name + ".norm2", h1, hw, ACT_SILU)
+        self.drop(h1)
+        if name + ".conv_shortcut" in self.eng.gemm_w:
+            sc = self.gemm(name + ".conv_shortcut", x, rows)
+            self.drop(x)
+        else:
+            sc = x
+        y = self.gemm(name + ".conv2", n2, rows, conv=conv, amode=A_CONV3_S1, residual=sc)
+        self.drop(n2)
+        self.drop(sc)
+        return y
+
+    def attention(self, name: str, x: _Act, hw: int) -> _Act:
+        Cc, rows = x.cols, x.rows
+        n = self.groupnorm(name + ".group_norm", x, hw, ACT_NONE)
+        qkv = self.gemm(name + ".qkv", n, rows)
+        self.drop(n)
+        o = self.act(rows, Cc)
+        ld, p0 = 3 * Cc, qkv.ptr
+        self.out.append(ops.Op("leco_attention_fwd", (p0, ld, hw * ld, p0 + 2 * Cc, ld, hw * ld, p0 + 4 * Cc, ld, hw * ld,
+                                                      o.ptr, Cc, hw * Cc, None, self.B, 1, hw, hw, Cc, Cc ** -0.5),
+                               keep=(qkv.blk, o.blk)))
+        self.drop(qkv)
+        y = self.gemm(name + ".to_out.0", o, rows, residual=x)
+        self.drop(o)
+        self.drop(x)
+        return y
+
+    def build(self) -> VAEPlan:
+        eng, cfg, B, h, w = self.eng, self.eng.cfg, self.B, self.h, self.w
+        dev, plan = eng.device, self.plan
+        lc = cfg.latent_channels
+        plan.x_in = torch.zeros(B, lc, h, w, dtype=torch.float32, device=dev)
+        z = torch.zeros(B, lc, h, w, dtype=bf16, device=dev)
+        self.out.append(ops.latent_affine(plan.x_in, eng.pq_w, eng.pq_b, z, B, h * w, lc, lc, 1.0 / cfg.scaling_factor))
+        ctop = cfg.block_out_channels[-1]
+        x = self.act(B * h * w, ctop)
+        self.out.append(ops.Op("leco_conv_in", (z.data_ptr(), eng.conv_in_w.data_ptr(), eng.conv_in_b.data_ptr(), x.ptr, B, h, w, lc,
+                                                ctop), keep=(z, x.blk)))
+        x = self.resnet("decoder.mid_block.resnets.0", x, h, w)
+        x = self.attention("decoder.mid_block.attentions.0", x, h * w)
+        x = self.resnet("decoder.mid_block.resnets.1", x, h, w)
+        hs, ws = h, w
+        for i, blk in enumerate(eng.vae.decoder.up_blocks):
+            for j in range(len(blk.resnets)):
+                x = self.resnet(f"decoder.up_blocks.{i}.resnets.{j}", x, hs, ws)
+            if blk.upsamplers is not None:
+                y = self.gemm(f"decoder.up_blocks.{i}.upsamplers.0.conv", x, B * 4 * hs * ws, conv=(B, 2 * hs, 2 * ws, hs, ws),
+                              amode=A_CONV3_UP2)
+                self.drop(x)
+                x, hs, ws = y, 2 * hs, 2 * ws
+        n = self.groupnorm("decoder.conv_norm_out", x, hs * ws, ACT_SILU)
+        self.drop(x)
+        plan.sample = torch.zeros(B, cfg.out_channels, hs, ws, dtype=torch.float32, device=dev)
+        plan.image = torch.zeros(B, hs, ws, cfg.out_channels, dtype=torch.uint8, device=dev)
+        self.out.append(ops.Op("leco_conv_out_rgb", (n.ptr, eng.conv_out_w.data_ptr(), eng.conv_out_b.data_ptr(),
+                                                     plan.sample.data_ptr(), plan.image.data_ptr(), B, hs, ws, n.cols), keep=(n.blk,)))
+        return plan
+
+
+def _graph_lib():
+    """The graph entry points of the library that is bound NOW (argument types are per loaded library object)."""
+    lib = hip.lib()
+    for nm, at in (("leco_graph_begin_capture", [C.c_void_p]), ("leco_graph_end_capture", [C.c_void_p, C.POINTER(C.c_void_p)]),
+                   ("leco_graph_launch", [C.c_void_p, C.c_void_p]), ("leco_graph_destroy", [C.c_void_p])):
+        fn = getattr(lib, nm)
+        fn.argtypes, fn.restype = at, C.c_int
+    return lib
+
+
+class VAEEngine:
+    """Packed device operands of one AutoencoderKL and its launch plans, keyed by (batch, h, w)."""
+
+    def __init__(self, vae: "AutoencoderKL", device: torch.device):
+        self.vae, self.cfg, self.device = vae, vae.cfg, device
+        cfg = self.cfg
+        if cfg.out_channels != 3:
+            raise ValueError(f"VAE decoder: out_channels = {cfg.out_channels}, the image epilogue writes RGB")
+        ctop = cfg.block_out_channels[-1]
+        if ctop not in WIDE_HEAD_DIMS:
+            raise ValueError(f"VAE decoder: the mid-block attention is one head of width {ctop}; the attention kernel is built for "
+                             f"{WIDE_HEAD_DIMS}")
+        if any(c % 32 for c in cfg.block_out_channels):
+            raise ValueError("VAE decoder: block_out_channels must be multiples of 32")
+        self.plans: Dict[tuple, VAEPlan] = {}
+        self.workspace = torch.empty(8 * 1024 * 1024, dtype=torch.float32, device=device)    # split-K partial slabs
+        f32 = lambda t: t.detach().float().to(device).contiguous()      # noqa: E731
+        self.gemm_w: Dict[str, Tuple[torch.Tensor, Optional[torch.Tensor]]] = {}
+        self.norm_p: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
+        for name, m in vae.named_modules():
+            if isinstance(m, nn.GroupNorm):
+                self.norm_p[name] = (f32(m.weight), f32(m.bias))
+            elif isinstance(m, Attention):
+                w = torch.cat([m.to_q.weight, m.to_k.weight, m.to_v.weight], 0).detach()
+                b = torch.cat([m.to_q.bias, m.to_k.bias, m.to_v.bias], 0)
+                self.gemm_w[name + ".qkv"] = (w.to(device, bf16).contiguous(), f32(b))
+                self.gemm_w[name + ".to_out.0"] = (m.to_out[0].weight.detach().to(device, bf16).contiguous(), f32(m.to_out[0].bias))
+            elif isinstance(m, nn.Conv2d) and name not in ("post_quant_conv", "decoder.conv_in", "decoder.conv_out"):
+                w = m.weight.detach()
+                w = w.permute(0, 2, 3, 1).reshape(w.shape[0], -1)           # [N][kh][kw][Cin]
+                self.gemm_w[name] = (w.to(device, bf16).contiguous(), f32(m.bias))
+        d = vae.decoder
+        lc = cfg.latent_channels
+        self.pq_w, self.pq_b = f32(vae.post_quant_conv.weight.reshape(lc, lc)), f32(vae.post_quant_conv.bias)
+        self.conv_in_w, self.conv_in_b = f32(d.conv_in.weight.detach().permute(1, 2, 3, 0)), f32(d.conv_in.bias)     # [Cin][3][3][Cout]
+        self.conv_out_w = d.conv_out.weight.detach().permute(0, 2, 3, 1).contiguous().to(device, bf16)                # [3][3][3][C]
+        self.conv_out_b = f32(d.conv_out.bias)
+
+    def plan(self, B: int, h: int, w: int) -> VAEPlan:
+        key = (B, h, w)
+        p = self.plans.get(key)
+        if p is None:
+            p = self.plans[key] = _Builder(self, B, h, w).build()
+        return p
+
+    def release(self) -> None:
+        if self.device.type == "cuda" and not hip.is_emulated():
+            torch.cuda.synchronize()
+            lib = _graph_lib()
+            for p in self.plans.values():
+                if p.graph is not None:
+                    lib.leco_graph_destroy(p.graph)
+        self.plans.clear()
+
+
+class AutoencoderKL(nn.Module):
+    """Decoder half of diffusers' ``AutoencoderKL`` (the encoder and ``quant_conv`` are not built).  `decode` takes the
+    sampler's latents as they are and divides by ``config.scaling_factor`` itself."""
+
+    def __init__(self, cfg: Optional[VAEConfig] = None):
+        super().__init__()
+        self.cfg = cfg or VAEConfig()
+        self.post_quant_conv = nn.Conv2d(self.cfg.latent_channels, self.cfg.latent_channels, 1)
+        self.decoder = Decoder(self.cfg)
+        self.use_graphs = False
+        self._engine: Optional[VAEEngine] = None
+        self.requires_grad_(False)
+
+    @property
+    def config(self) -> VAEConfig:
+        return self.cfg
+
+    @property
+    def device(self):
+        return self.post_quant_conv.weight.device
+
+    def set_precision(self, precision) -> "AutoencoderKL":
+        """The decoder computes in bf16 with fp32 accumulation whatever dtype its parameters are held in."""
+        if precision not in ("bfloat16", "bf16", torch.bfloat16):
+            raise NotImplementedError(f"VAE decoder: compute precision {precision!r} is not implemented (bfloat16 only; "
+                                      "`train.precision: float32` does not extend to the decoder)")
+        return self
+
+    def engine(self) -> VAEEngine:
+        if self._engine is None or self._engine.device != self.device:
+            self._engine = VAEEngine(self, self.device)
+        return self._engine
+
+    def release(self) -> None:
+        if self._engine is not None:
+            self._engine.release()
+            self._engine = None
+
+    def _run(self, plan: VAEPlan) -> None:
+        if not (self.use_graphs and self.device.type == "cuda" and not hip.is_emulated()) or ops._TRACE_OPS:
+            ops.run_plan(plan.ops)
+            return
+        lib = _graph_lib()
+        cur = torch.cuda.current_stream()
+        if plan.graph is None:
+            ops.run_plan(plan.ops)      # first use: eager once (one-time kernel attributes are set outside the capture)
+            side = self.__dict__.get("_capture_stream")
+            if side is None:
+                side = self.__dict__["_capture_stream"] = torch.cuda.Stream()
+            side.wait_stream(cur)
+            sp = side.cuda_stream
+            hip.check(lib.leco_graph_begin_capture(sp), "graph begin")
+            try:
+                ops.run_plan(plan.ops, sp)
+            finally:
+                gh = C.c_void_p()
+                hip.check(lib.leco_graph_end_capture(sp, C.byref(gh)), "graph end")
+            plan.graph = gh
+        hip.check(lib.leco_graph_launch(plan.graph, cur.cuda_stream), "graph launch")
+
+    def _decode(self, latents: torch.Tensor) -> VAEPlan:
+        if latents.ndim != 4 or latents.shape[1] != self.cfg.latent_channels:
+            raise ValueError(f"VAE decode: latents must be (B, {self.cfg.latent_channels}, h, w), got {tuple(latents.shape)}")
+        B, _, h, w = latents.shape
+        plan = self.engine().plan(B, h, w)
+        plan.x_in.copy_(latents)
+        self._run(plan)
+        return plan
+
+    @torch.no_grad()
+    def decode(self, latents: torch.Tensor, return_dict: bool = True):
+        """``latents``: the sampler's output (B, 4, h, w), NOT divided by the scaling factor (the division is folded into the
+        first launch).  Returns an object with ``.sample``: fp32 (B, 3, 8h, 8w), nominally in [-1, 1]."""
+        sample = self._decode(latents).sample.clone()
+        return DecoderOutput(sample) if return_dict else (sample,)
+
+    @torch.no_grad()
+    def decode_to_uint8(self, latents: torch.Tensor) -> torch.Tensor:
+        """(B, 8h, 8w, 3) uint8 pixels: floor(clamp(sample / 2 + 0.5, 0, 1) * 255 + 0.5), from the output convolution's epilogue."""
+        return self._decode(latents).image.clone()
+
+
+def init_synthetic_vae_(vae: AutoencoderKL, seed: int = 4321) -> AutoencoderKL:
+    from .model_util import init_synthetic_
+    init_synthetic_(vae, seed)
+    return vae
+
+
+# ---- PNG -----------------------------------------------------------------------------------------------------------------------
+def _png_bytes(img) -> bytes:
+    h, w, _ = img.shape
+    raw = b"".join(b"\x00" + img[y].tobytes() for y in range(h))      # filter type 0 on every scanline
+
+    def chunk(tag: bytes, data: bytes) -> bytes:
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xffffffff)
+    return (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0))
+            + chunk(b"IDAT", zlib.compress(raw, 6)) + chunk(b"IEND", b""))
+
+
+def save_png(uint8_hwc, path: str) -> None:
+    """Write one (H, W, 3) uint8 image as an 8-bit RGB PNG: PIL when importable, else a zlib writer of its own."""
+    t = torch.as_tensor(uint8_hwc)
+    if t.ndim != 3 or t.shape[2] != 3 or t.dtype != torch.uint8:
+        raise ValueError(f"save_png: expected (H, W, 3) uint8, got {tuple(t.shape)} {t.dtype}")
+    arr = t.detach().cpu().contiguous().numpy()
+    try:
+        from PIL import Image
+    except ImportError:
+        with open(path, "wb") as f:
+            f.write(_png_bytes(arr))
+        return
+    Image.fromarray(arr, "RGB").save(path, format="PNG")

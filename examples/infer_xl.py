@@ -49,10 +49,13 @@ def main(argv=None):
     ap.add_argument("--out", default="latents.safetensors")
     ap.add_argument("--image", default=None, help="decode the latents with the VAE and write this PNG")
     ap.add_argument("--vae", default=None, help="VAE for --image (default: the model's vae/ folder, or its synthetic VAE)")
+    ap.add_argument("--native_text_encoder", action="store_true",
+                    help="encode the prompts with the native CLIP text encoder (leco_amd.clip, bf16 only) instead of transformers")
     args = ap.parse_args(argv)
     dev = torch.device(args.device)
     dtype = torch.bfloat16
-    tokenizers, text_encoders, unet, sched = model_util.load_models_xl(args.model, scheduler_name="ddim")
+    tokenizers, text_encoders, unet, sched = model_util.load_models_xl(args.model, scheduler_name="ddim",
+                                                                        native_text_encoder=args.native_text_encoder)
     for te in text_encoders:
         te.to(dev, dtype=dtype)
         te.eval()

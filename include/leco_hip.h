@@ -48,8 +48,13 @@ enum {
  * weight / bias / w_ext ROWS interleaved in blocks of 64 -- row 128 j + r holds value row 64 j + r (r < 64) or gate
  * row F + 64 j + (r - 64) (r >= 64) -- so one 128-column tile owns a value block and its gate block: the epilogue
  * writes value * gelu(gate) (erf form) as bf16 [M][F] (row stride ldc) and the [M][2F] intermediate never
- * exists.  Needs n % 128 == 0, c != NULL, no residual / rowbias / c_f32, no split-K. */
-enum { LECO_ACT_NONE = 0, LECO_ACT_SILU = 1, LECO_ACT_GEGLU = 2 };
+ * exists.  Needs n % 128 == 0, c != NULL, no residual / rowbias / c_f32, no split-K.
+ * LECO_ACT_QUICK_GELU: z sigmoid(1.702 z) (CLIP-L's MLP, transformers' QuickGELUActivation); LECO_ACT_GELU: z Phi(z), the
+ * erf form (OpenCLIP-H / bigG's MLP; the same gelu the GEGLU epilogue applies to its gate).  Both are pointwise like
+ * LECO_ACT_SILU -- C = act(acc + bias + rowbias + residual) -- on every tile id of leco_gemm / leco_gemm_tile /
+ * leco_gemm_ex, conv gathers included; under split-K the finishing kernel applies them.  leco_f32_gemm rejects them
+ * (-EINVAL); leco_xgemm and the stripe chains carry no act argument.  Any other value of act is -EINVAL. */
+enum { LECO_ACT_NONE = 0, LECO_ACT_SILU = 1, LECO_ACT_GEGLU = 2, LECO_ACT_QUICK_GELU = 3, LECO_ACT_GELU = 4 };
 
 typedef struct leco_gemm_args {
     const void* a0;       /* bf16 */
@@ -189,7 +194,7 @@ int leco_rowgroup_sum(const void* x, int64_t ldx, float* out, int64_t ldo, int32
  * LayerNorm in BasicTransformerBlock; call site train_util.py:156-160; dgrads train_lora.py:279).
  * x may be the channel concat [x0 | x1] (x1 == NULL: single source).  stats / bstats are
  * fp32 [batch][groups][2] scratch ({sum, sumsq} resp. {sum dxhat, sum dxhat*xhat}); the
- * forward stats must be kept for the backward.  act: LECO_ACT_NONE / LECO_ACT_SILU.
+ * forward stats must be kept for the backward.  act: LECO_ACT_NONE / LECO_ACT_SILU (any other value: -EINVAL).
  * ---------------------------------------------------------------------- */
 #define LECO_GN_STATS_FLOATS(batch, groups) ((int64_t)(batch) * (groups) * 2 * 257)
 int leco_groupnorm_fwd(const void* x0, int64_t ld0, const void* x1, int64_t ld1, int32_t c0,
@@ -245,9 +250,28 @@ int leco_attention_bwd(const void* q, int64_t ldq, int64_t bsq, const void* k, i
                        int64_t bsdv, int32_t batch, int32_t heads, int32_t sq, int32_t skv,
                        int32_t head_dim, float scale, leco_stream_t stream);
 
+/* Causal self-attention core softmax(Q K^T * scale + causal) V per (batch, head): key j contributes to query i only for
+ * j <= i.  Replaces the attention of transformers' CLIPTextModel layers (text_encoder(...) in train_util.py:32-62).  Same
+ * operand convention as leco_attention_fwd (bf16, token stride ld*, batch stride bs*, head h in columns [h*d, (h+1)*d);
+ * q | k | v may be column views of one fused [B][S][3C] buffer); one sequence length s for queries and keys,
+ * 1 <= s <= LECO_CAUSAL_ATTN_MAX_S, head_dim == 64.  bf16 MFMA, fp32 accumulation and softmax; no score matrix in global
+ * memory; a workgroup owns 16 query rows and stages only the keys up to its last row: key tiles above the diagonal are
+ * never read, the tile on the diagonal is masked per element. */
+#define LECO_CAUSAL_ATTN_MAX_S 128
+int leco_attention_causal_fwd(const void* q, int64_t ldq, int64_t bsq, const void* k, int64_t ldk, int64_t bsk,
+                              const void* v, int64_t ldv, int64_t bsv, void* o, int64_t ldo, int64_t bso, int32_t batch,
+                              int32_t heads, int32_t s, int32_t head_dim, float scale, leco_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * Elementwise / small kernels.
  * ---------------------------------------------------------------------- */
+/* Row gather (+ periodic add): out[i][:] = table[idx[i]][:] (+ pos[i % period][:]), i < n; table / pos / out bf16 with row
+ * strides ldt / ldp / ldo (multiples of 8), c % 8 == 0, the sum formed in fp32 and rounded once.  idx: DEVICE int32 [n],
+ * every entry in [0, rows) (the caller validates; the kernel clamps, it never reads outside the table).  With pos it is
+ * CLIPTextEmbeddings (token_embedding(ids) + position_embedding, period = sequence length); with pos == NULL it gathers
+ * the EOS row of each sample for the pooled output (last_hidden_state[arange(B), eos_pos]). */
+int leco_embed_rows(const void* table, int64_t ldt, int32_t rows, const int32_t* idx, const void* pos, int64_t ldp,
+                    int32_t period, void* out, int64_t ldo, int32_t n, int32_t c, leco_stream_t stream);
 /* GEGLU (diffusers FeedForward ff.net.0): y[m][f] = u[m][f] * gelu_erf(u[m][F+f]) */
 int leco_geglu_fwd(const void* u, int64_t ldu, void* y, int64_t ldy, int32_t m, int32_t f,
                    leco_stream_t stream);

@@ -22,7 +22,7 @@ def _sources():
 
 def _digest(src: str) -> str:
     h = hashlib.sha1(" ".join(FLAGS).encode())
-    deps = [src, os.path.join(ROOT, "include", "leco_hip.h"), os.path.join(CSRC, "common.h"),
+    deps = [src, os.path.join(ROOT, "include", "leco_hip.h"), os.path.join(CSRC, "common.h"), os.path.join(CSRC, "act.h"),
             os.path.join(CSRC, "prims", "leco_prims.h")]
     for d in deps:
         with open(d, "rb") as f:

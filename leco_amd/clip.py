@@ -1,0 +1,426 @@
+"""The CLIP text encoder (transformers' ``CLIPTextModel`` / ``CLIPTextModelWithProjection``: CLIP-L of SD1.x / SDXL,
+OpenCLIP-H of SD2.x, OpenCLIP-bigG of SDXL) on the HIP kernels: token ids -> prompt embeddings, what the reference's
+``train_util.py:32-62`` (``text_encode`` / ``text_encode_xl``) gets from ``text_encoder(tokens)``.
+
+The module tree only HOLDS weights under the transformers parameter names (``text_model.embeddings.token_embedding``,
+``text_model.embeddings.position_embedding``, ``text_model.encoder.layers.N.{self_attn.{q,k,v,out}_proj, layer_norm1,
+layer_norm2, mlp.fc1, mlp.fc2}``, ``text_model.final_layer_norm``, ``text_projection``), so an HF state dict -- or the
+output of ``ckpt_convert.convert_ldm_clip`` / ``convert_open_clip`` -- loads with ``load_state_dict`` as is.  A call runs
+a forward-only launch plan built from ``ops.*`` per (batch, sequence length): bf16 activations, fp32 accumulation;
+replayed from a hipGraph when ``use_graphs`` is set.
+
+    token + position embedding                           leco_embed_rows
+    N x  layer_norm1                                     leco_layernorm_fwd
+         fused q|k|v Linear                              leco_gemm
+         causal attention, 64-wide heads                 leco_attention_causal_fwd
+         out_proj + residual                             leco_gemm
+         layer_norm2                                     leco_layernorm_fwd
+         fc1 + quick-GELU / GELU                         leco_gemm (LECO_ACT_QUICK_GELU / LECO_ACT_GELU)
+         fc2 + residual                                  leco_gemm
+    final_layer_norm                                     leco_layernorm_fwd
+    EOS row per sample                                   leco_embed_rows (no position table)
+    text_projection (no bias)                            leco_gemm
+
+The tokenizer stays transformers' ``CLIPTokenizer``; there is no backward (no text-encoder LoRA / textual inversion).
+"""
+from __future__ import annotations
+
+import ctypes as C
+import json
+from dataclasses import dataclass, fields
+from typing import Dict, List, Optional, Tuple
+
+import torch
+from torch import nn
+
+from . import hip, ops
+from .hip import ACT_GELU, ACT_NONE, ACT_QUICK_GELU, gemm_args
+
+bf16 = torch.bfloat16
+LN_EPS = 1e-5
+HEAD_DIM = 64                    # what leco_attention_causal_fwd is built for: every CLIP tower SD uses
+ACTS = {"quick_gelu": ACT_QUICK_GELU, "gelu": ACT_GELU}
+
+
+@dataclass
+class CLIPTextConfig:
+    vocab_size: int = 49408
+    hidden_size: int = 768
+    intermediate_size: int = 3072
+    num_hidden_layers: int = 12
+    num_attention_heads: int = 12
+    max_position_embeddings: int = 77
+    hidden_act: str = "quick_gelu"
+    projection_dim: int = 768
+    eos_token_id: int = 2
+    bos_token_id: int = 0
+    layer_norm_eps: float = LN_EPS
+
+    def __post_init__(self):
+        if self.hidden_act not in ACTS:
+            raise ValueError(f"CLIP text encoder: hidden_act {self.hidden_act!r} is not one of {sorted(ACTS)}")
+        if self.num_attention_heads <= 0 or self.hidden_size != HEAD_DIM * self.num_attention_heads:
+            raise ValueError(f"CLIP text encoder: hidden_size {self.hidden_size} / num_attention_heads {self.num_attention_heads} "
+                             f"must be {HEAD_DIM} (the causal attention kernel is built for {HEAD_DIM}-wide heads)")
+        if self.max_position_embeddings > ops.CAUSAL_ATTN_MAX_S:
+            raise ValueError(f"CLIP text encoder: max_position_embeddings {self.max_position_embeddings} exceeds the causal "
+                             f"attention kernel's {ops.CAUSAL_ATTN_MAX_S} tokens")
+        if self.intermediate_size % 64 or self.projection_dim % 8 or self.num_hidden_layers < 1:
+            raise ValueError("CLIP text encoder: intermediate_size must be a multiple of 64, projection_dim of 8, and there "
+                             "must be at least one layer")
+
+    @classmethod
+    def from_dict(cls, d: dict, **override) -> "CLIPTextConfig":
+        known = {f.name for f in fields(cls)}
+        kw = {k: v for k, v in d.items() if k in known and v is not None}
+        kw.update(override)
+        return cls(**kw)
+
+    @classmethod
+    def from_json(cls, path: str, **override) -> "CLIPTextConfig":
+        """A diffusers ``text_encoder/config.json``."""
+        with open(path) as f:
+            return cls.from_dict(json.load(f), **override)
+
+
+def clip_l_config(**kw) -> CLIPTextConfig:
+    return CLIPTextConfig(**{**dict(eos_token_id=49407, bos_token_id=49406), **kw})
+
+
+def open_clip_h_config(**kw) -> CLIPTextConfig:
+    """SD2.x: 24 layers in the tower, 23 used (the penultimate layer's output)."""
+    return CLIPTextConfig(**{**dict(hidden_size=1024, intermediate_size=4096, num_hidden_layers=23, num_attention_heads=16,
+                                    hidden_act="gelu", projection_dim=1024, eos_token_id=49407, bos_token_id=49406), **kw})
+
+
+def open_clip_bigg_config(**kw) -> CLIPTextConfig:
+    return CLIPTextConfig(**{**dict(hidden_size=1280, intermediate_size=5120, num_hidden_layers=32, num_attention_heads=20,
+                                    hidden_act="gelu", projection_dim=1280, eos_token_id=49407, bos_token_id=49406), **kw})
+
+
+# ---- weight holders (transformers names) ---------------------------------------------------------------------------------------
+class CLIPTextEmbeddings(nn.Module):
+    def __init__(self, cfg: CLIPTextConfig):
+        super().__init__()
+        self.token_embedding = nn.Embedding(cfg.vocab_size, cfg.hidden_size)
+        self.position_embedding = nn.Embedding(cfg.max_position_embeddings, cfg.hidden_size)
+
+
+class CLIPAttention(nn.Module):
+    def __init__(self, c: int):
+        super().__init__()
+        self.k_proj, self.v_proj, self.q_proj, self.out_proj = nn.Linear(c, c), nn.Linear(c, c), nn.Linear(c, c), nn.Linear(c, c)
+
+
+class CLIPMLP(nn.Module):
+    def __init__(self, c: int, f: int):
+        super().__init__()
+        self.fc1, self.fc2 = nn.Linear(c, f), nn.Linear(f, c)
+
+
+class CLIPEncoderLayer(nn.Module):
+    def __init__(self, cfg: CLIPTextConfig):
+        super().__init__()
+        c = cfg.hidden_size
+        self.self_attn = CLIPAttention(c)
+        self.layer_norm1 = nn.LayerNorm(c, eps=cfg.layer_norm_eps)
+        self.mlp = CLIPMLP(c, cfg.intermediate_size)
+        self.layer_norm2 = nn.LayerNorm(c, eps=cfg.layer_norm_eps)
+
+
+class CLIPEncoder(nn.Module):
+    def __init__(self, cfg: CLIPTextConfig):
+        super().__init__()
+        self.layers = nn.ModuleList([CLIPEncoderLayer(cfg) for _ in range(cfg.num_hidden_layers)])
+
+
+class CLIPTextTransformer(nn.Module):
+    def __init__(self, cfg: CLIPTextConfig):
+        super().__init__()
+        self.embeddings = CLIPTextEmbeddings(cfg)
+        self.encoder = CLIPEncoder(cfg)
+        self.final_layer_norm = nn.LayerNorm(cfg.hidden_size, eps=cfg.layer_norm_eps)
+
+
+class CLIPTextOutput:
+    """What ``train_util.text_encode`` / ``text_encode_xl`` read: ``[0]`` (``last_hidden_state``, or ``text_embeds`` for the
+    projection class), ``.last_hidden_state``, ``.pooler_output``, ``.text_embeds``, ``.hidden_states``."""
+
+    def __init__(self, first: str, last_hidden_state, pooler_output, text_embeds=None, hidden_states=None):
+        self._first = first
+        self.last_hidden_state, self.pooler_output = last_hidden_state, pooler_output
+        self.text_embeds, self.hidden_states = text_embeds, hidden_states
+
+    def _tuple(self):
+        head = (self.text_embeds, self.last_hidden_state) if self._first == "text_embeds" else \
+            (self.last_hidden_state, self.pooler_output)
+        return head + ((self.hidden_states,) if self.hidden_states is not None else ())
+
+    def __getitem__(self, i):
+        return self._tuple()[i]
+
+    def __iter__(self):
+        return iter(self._tuple())
+
+
+# ---- launch plan ---------------------------------------------------------------------------------------------------------------
+class CLIPPlan:
+    def __init__(self):
+        self.ops: List[ops.Op] = []
+        self.names: List[str] = []               # one label per launch (tools/bench_clip.py --per-op)
+        self.graph = None
+        self.ids: torch.Tensor = None            # int32 [B * S]: token ids
+        self.eos_idx: torch.Tensor = None        # int32 [B]: row b * S + (EOS position of sample b) of the hidden states
+        self.hidden: List[torch.Tensor] = []     # bf16 [B * S][C]: the embeddings, then every layer's output
+        self.last: torch.Tensor = None           # bf16 [B * S][C]: final_layer_norm of the last layer's output
+        self.pooled: torch.Tensor = None         # bf16 [B][C]
+        self.text_embeds: Optional[torch.Tensor] = None     # bf16 [B][projection_dim]
+        self.keep: list = []
+
+
+def _graph_lib():
+    """The graph entry points of the library that is bound NOW (argument types are per loaded library object)."""
+    lib = hip.lib()
+    for nm, at in (("leco_graph_begin_capture", [C.c_void_p]), ("leco_graph_end_capture", [C.c_void_p, C.POINTER(C.c_void_p)]),
+                   ("leco_graph_launch", [C.c_void_p, C.c_void_p]), ("leco_graph_destroy", [C.c_void_p])):
+        fn = getattr(lib, nm)
+        fn.argtypes, fn.restype = at, C.c_int
+    return lib
+
+
+class CLIPEngine:
+    """Packed device operands of one text encoder and its launch plans, keyed by (batch, sequence length)."""
+
+    def __init__(self, model: "CLIPTextModel", device: torch.device):
+        self.cfg, self.device = model.cfg, device
+        self.plans: Dict[tuple, CLIPPlan] = {}
+        self.workspace = torch.empty(2 * 1024 * 1024, dtype=torch.float32, device=device)      # split-K partial slabs
+        f32 = lambda t: t.detach().float().to(device).contiguous()      # noqa: E731
+        wb = lambda t: t.detach().to(device, bf16).contiguous()          # noqa: E731
+        tm = model.text_model
+        self.tok, self.pos = wb(tm.embeddings.token_embedding.weight), wb(tm.embeddings.position_embedding.weight)
+        self.gemm_w: Dict[str, Tuple[torch.Tensor, Optional[torch.Tensor]]] = {}
+        self.norm_p: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
+        for i, l in enumerate(tm.encoder.layers):
+            a = l.self_attn
+            self.gemm_w[f"{i}.qkv"] = (wb(torch.cat([a.q_proj.weight, a.k_proj.weight, a.v_proj.weight], 0)),
+                                       f32(torch.cat([a.q_proj.bias, a.k_proj.bias, a.v_proj.bias], 0)))
+            self.gemm_w[f"{i}.out"] = (wb(a.out_proj.weight), f32(a.out_proj.bias))
+            self.gemm_w[f"{i}.fc1"] = (wb(l.mlp.fc1.weight), f32(l.mlp.fc1.bias))
+            self.gemm_w[f"{i}.fc2"] = (wb(l.mlp.fc2.weight), f32(l.mlp.fc2.bias))
+            self.norm_p[f"{i}.ln1"] = (f32(l.layer_norm1.weight), f32(l.layer_norm1.bias))
+            self.norm_p[f"{i}.ln2"] = (f32(l.layer_norm2.weight), f32(l.layer_norm2.bias))
+        self.norm_p["final"] = (f32(tm.final_layer_norm.weight), f32(tm.final_layer_norm.bias))
+        proj = getattr(model, "text_projection", None)
+        self.proj_w = None if proj is None else wb(proj.weight)
+
+    # -- plan construction ----------------------------------------------------------------------------------------------------
+    def _build(self, B: int, S: int) -> CLIPPlan:
+        cfg, dev = self.cfg, self.device
+        Cw, Fw, H, M = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads, B * S
+        p = CLIPPlan()
+        buf = lambda rows, cols: torch.zeros(rows, cols, dtype=bf16, device=dev)      # noqa: E731
+        p.ids = torch.zeros(M, dtype=torch.int32, device=dev)
+        p.eos_idx = torch.zeros(B, dtype=torch.int32, device=dev)
+        p.hidden = [buf(M, Cw) for _ in range(cfg.num_hidden_layers + 1)]
+        n, qkv, att, h1, u = buf(M, Cw), buf(M, 3 * Cw), buf(M, Cw), buf(M, Cw), buf(M, Fw)
+        mean, rstd = torch.zeros(M, device=dev), torch.zeros(M, device=dev)
+        p.keep = [n, qkv, att, h1, u, mean, rstd]
+
+        def add(name, op):
+            p.ops.append(op)
+            p.names.append(name)
+
+        def ln(name, x, y):
+            g, b = self.norm_p[name]
+            add("layernorm", ops.layernorm_fwd(x, Cw, g, b, cfg.layer_norm_eps, M, Cw, y, Cw, mean, rstd))
+
+        def gemm(label, name, x, y, k, act=ACT_NONE, residual=None):
+            w, bias = self.gemm_w[name]
+            g = gemm_args(x, w, y, m=M, n=w.shape[0], k=k, bias=bias, residual=residual, act=act)
+            add(label, ops.gemm(g, keep=(w, bias, x, y, residual), ws=self.workspace))
+
+        add("embed", ops.embed_rows(self.tok, Cw, cfg.vocab_size, p.ids, self.pos, Cw, S, p.hidden[0], Cw, M, Cw))
+        for i in range(cfg.num_hidden_layers):
+            x, y = p.hidden[i], p.hidden[i + 1]
+            ln(f"{i}.ln1", x, n)
+            gemm("qkv", f"{i}.qkv", n, qkv, Cw)
+            q0, ld = qkv.data_ptr(), 3 * Cw
+            add("attention", ops.attention_causal_fwd(q0, ld, S * ld, q0 + 2 * Cw, ld, S * ld, q0 + 4 * Cw, ld, S * ld, att.data_ptr(),
+                                                      Cw, S * Cw, B, H, S, HEAD_DIM, HEAD_DIM ** -0.5, keep=(qkv, att)))
+            gemm("out_proj", f"{i}.out", att, h1, Cw, residual=x)
+            ln(f"{i}.ln2", h1, n)
+            gemm("fc1", f"{i}.fc1", n, u, Cw, act=ACTS[cfg.hidden_act])
+            gemm("fc2", f"{i}.fc2", u, y, Fw, residual=h1)
+        p.last = buf(M, Cw)
+        ln("final", p.hidden[-1], p.last)
+        p.pooled = buf(B, Cw)
+        add("eos_gather", ops.embed_rows(p.last, Cw, M, p.eos_idx, None, 0, 1, p.pooled, Cw, B, Cw))
+        if self.proj_w is not None:
+            P = self.proj_w.shape[0]
+            p.text_embeds = buf(B, P)
+            g = gemm_args(p.pooled, self.proj_w, p.text_embeds, m=B, n=P, k=Cw)
+            add("projection", ops.gemm(g, keep=(self.proj_w, p.pooled, p.text_embeds), ws=self.workspace))
+        return p
+
+    def plan(self, B: int, S: int) -> CLIPPlan:
+        key = (B, S)
+        p = self.plans.get(key)
+        if p is None:
+            p = self.plans[key] = self._build(B, S)
+        return p
+
+    def release(self) -> None:
+        if self.device.type == "cuda" and not hip.is_emulated():
+            torch.cuda.synchronize()
+            lib = _graph_lib()
+            for p in self.plans.values():
+                if p.graph is not None:
+                    lib.leco_graph_destroy(p.graph)
+        self.plans.clear()
+
+
+class CLIPTextModel(nn.Module):
+    """transformers' ``CLIPTextModel``, forward only.  Compute is bf16 with fp32 accumulation whatever dtype the parameters
+    are held in; outputs come back in that dtype."""
+    _first = "last_hidden_state"
+
+    def __init__(self, cfg: Optional[CLIPTextConfig] = None):
+        super().__init__()
+        self.cfg = cfg or CLIPTextConfig()
+        self.text_model = CLIPTextTransformer(self.cfg)
+        self.use_graphs = True
+        self._engine: Optional[CLIPEngine] = None
+        self.requires_grad_(False)
+
+    @property
+    def config(self) -> CLIPTextConfig:
+        return self.cfg
+
+    @property
+    def device(self):
+        return self.text_model.final_layer_norm.weight.device
+
+    @property
+    def dtype(self):
+        return self.text_model.final_layer_norm.weight.dtype
+
+    def load_state_dict(self, state_dict, strict: bool = True, **kw):
+        """A missing or unexpected key is a KeyError naming it (``position_ids``, a buffer of older checkpoints, is ignored)."""
+        sd = {k: v for k, v in state_dict.items() if not k.endswith("position_ids")}
+        missing, unexpected = super().load_state_dict(sd, strict=False, **kw)
+        if strict and missing:
+            raise KeyError(f"CLIP text encoder: the state dict lacks {missing[0]!r}"
+                           + (f" (and {len(missing) - 1} more)" if len(missing) > 1 else ""))
+        if strict and unexpected:
+            raise KeyError(f"CLIP text encoder: unexpected key {unexpected[0]!r}"
+                           + (f" (and {len(unexpected) - 1} more)" if len(unexpected) > 1 else ""))
+        self.release()
+        return missing, unexpected
+
+    def set_precision(self, precision) -> "CLIPTextModel":
+        if precision not in ("bfloat16", "bf16", torch.bfloat16):
+            raise NotImplementedError(f"CLIP text encoder: compute precision {precision!r} is not implemented (bfloat16 only; "
+                                      "`train.precision: float32` does not extend to the native text encoder)")
+        return self
+
+    def _apply(self, fn, *a, **kw):
+        out = super()._apply(fn, *a, **kw)
+        self.release()          # the packed operands follow the parameters: rebuilt on the next call
+        return out
+
+    def engine(self) -> CLIPEngine:
+        if self._engine is None or self._engine.device != self.device:
+            self.release()
+            self._engine = CLIPEngine(self, self.device)
+        return self._engine
+
+    def release(self) -> None:
+        if self.__dict__.get("_engine") is not None:
+            self._engine.release()
+            self._engine = None
+
+    def _eager(self) -> bool:
+        return not (self.use_graphs and self.device.type == "cuda" and not hip.is_emulated()) or ops._TRACE_OPS
+
+    def _run(self, plan: CLIPPlan) -> None:
+        if self._eager():
+            ops.run_plan(plan.ops)
+            return
+        lib = _graph_lib()
+        cur = torch.cuda.current_stream()
+        if plan.graph is None:
+            ops.run_plan(plan.ops)      # first use: eager once (one-time kernel attributes are set outside the capture)
+            side = self.__dict__.get("_capture_stream")
+            if side is None:
+                side = self.__dict__["_capture_stream"] = torch.cuda.Stream()
+            side.wait_stream(cur)
+            sp = side.cuda_stream
+            hip.check(lib.leco_graph_begin_capture(sp), "graph begin")
+            try:
+                ops.run_plan(plan.ops, sp)
+            finally:
+                gh = C.c_void_p()
+                hip.check(lib.leco_graph_end_capture(sp, C.byref(gh)), "graph end")
+            plan.graph = gh
+        hip.check(lib.leco_graph_launch(plan.graph, cur.cuda_stream), "graph launch")
+
+    def eos_positions(self, ids: torch.Tensor) -> torch.Tensor:
+        """transformers' pooling rule: the first position equal to ``eos_token_id``, or argmax of the ids for the legacy
+        configs that say ``eos_token_id == 2``."""
+        if self.cfg.eos_token_id == 2:
+            return ids.argmax(dim=-1)
+        return (ids == self.cfg.eos_token_id).int().argmax(dim=-1)
+
+    def _encode(self, input_ids) -> CLIPPlan:
+        ids = torch.as_tensor(input_ids)
+        if ids.ndim != 2 or ids.dtype.is_floating_point or ids.dtype == torch.bool:
+            raise ValueError(f"CLIP text encoder: input_ids must be an integer [batch][tokens] tensor, got {tuple(ids.shape)} {ids.dtype}")
+        B, S = ids.shape
+        if not 1 <= S <= self.cfg.max_position_embeddings or B < 1:
+            raise ValueError(f"CLIP text encoder: {S} tokens per prompt, max_position_embeddings is {self.cfg.max_position_embeddings}")
+        host = ops.check_row_ids(ids, self.cfg.vocab_size, "input_ids")          # IndexError before any launch
+        eos = self.eos_positions(host.view(B, S).long()) + torch.arange(B) * S
+        plan = self.engine().plan(B, S)
+        plan.ids.copy_(host)
+        plan.eos_idx.copy_(eos.to(torch.int32))
+        self._run(plan)
+        return plan
+
+    @torch.no_grad()
+    def forward(self, input_ids, output_hidden_states: bool = False, **kw) -> CLIPTextOutput:
+        plan = self._encode(input_ids)
+        B, S = torch.as_tensor(input_ids).shape
+        dt = self.dtype
+        out = lambda t, *shape: t.view(*shape).to(dt, copy=True)      # noqa: E731  (the plan's buffers are reused by the next call)
+        hs = tuple(out(h, B, S, -1) for h in plan.hidden) if output_hidden_states else None
+        te = None if plan.text_embeds is None else out(plan.text_embeds, B, -1)
+        return CLIPTextOutput(self._first, out(plan.last, B, S, -1), out(plan.pooled, B, -1), te, hs)
+
+
+class CLIPTextModelWithProjection(CLIPTextModel):
+    """transformers' ``CLIPTextModelWithProjection``: ``[0]`` / ``.text_embeds`` = text_projection(pooled output), no bias."""
+    _first = "text_embeds"
+
+    def __init__(self, cfg: Optional[CLIPTextConfig] = None):
+        super().__init__(cfg)
+        self.text_projection = nn.Linear(self.cfg.hidden_size, self.cfg.projection_dim, bias=False)
+        self.requires_grad_(False)
+
+
+def init_synthetic_clip_(model: CLIPTextModel, seed: int = 2468) -> CLIPTextModel:
+    """Seeded random weights of the scale of a trained tower (embeddings ~ N(0, 0.02), Linear U(+-1/sqrt(fan_in)),
+    LayerNorm gamma near 1): measurement tools and tests, no checkpoint exists on the build boxes."""
+    g = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        for name, p in model.named_parameters():
+            if "embedding" in name:
+                p.copy_(torch.randn(p.shape, generator=g) * 0.02)
+            elif p.ndim == 2:
+                p.copy_((torch.rand(p.shape, generator=g) * 2 - 1) / p.shape[1] ** 0.5)
+            elif "norm" in name and name.endswith("weight"):
+                p.copy_(1.0 + 0.1 * torch.randn(p.shape, generator=g))
+            else:
+                p.copy_(0.02 * torch.randn(p.shape, generator=g))
+    model.release()
+    return model

@@ -37,6 +37,7 @@
 #include <hip/hip_runtime.h>
 #include <leco_prims.h>
 
+#include "act.h"
 #include "common.h"
 
 namespace leco {
@@ -508,10 +509,7 @@ __global__ __launch_bounds__(512) void conv_patch_kernel(const leco_gemm_args p,
                     v[2 * q + 1] += bf2f((bf16_t)(rr[q] >> 16));
                 }
             }
-            if (p.act == LECO_ACT_SILU) {
-#pragma unroll
-                for (int q = 0; q < 8; ++q) v[q] = v[q] / (1.f + __expf(-v[q]));
-            }
+            apply_act(v, p.act);
             if (cp) {
                 const u32x4 o = {pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]), pack_bf2(v[4], v[5]), pack_bf2(v[6], v[7])};
                 *(u32x4*)(cp + (int64_t)m * p.ldc + n) = o;

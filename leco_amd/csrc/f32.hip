@@ -729,6 +729,7 @@ extern "C" int leco_f32_groupnorm_fwd(const void* x0, int64_t ld0, const void* x
                                       const float* beta, int32_t batch, int32_t hw, int32_t c, int32_t groups, float eps, int32_t act,
                                       float* stats, void* y, int64_t ldy, leco_stream_t stream) {
     if (groups <= 0 || c % groups) return fail(-EINVAL, "leco_f32_groupnorm: c=%d groups=%d", c, groups);
+    if (act != LECO_ACT_NONE && act != LECO_ACT_SILU) return fail(-EINVAL, "leco_f32_groupnorm: act %d unsupported (NONE / SILU)", act);
     GnSrcF s{(const float*)x0, (const float*)x1, ld0, ld1, x1 ? c0 : c};
     hipLaunchKernelGGL(gn_fwd_f32_kernel, dim3(groups, batch), dim3(256), 0, LECO_STREAM, s, gamma, beta, hw, c, groups, eps, act, stats,
                        (float*)y, ldy);

@@ -33,6 +33,7 @@
 #include <hip/hip_runtime.h>
 #include <leco_prims.h>
 
+#include "act.h"
 #include "common.h"
 
 namespace leco {
@@ -52,18 +53,6 @@ __device__ const u32x4 g_zero_page[4] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}, {0u
 
 __device__ __forceinline__ int lds_off(int row, int chunk) {
     return row * BK + ((chunk ^ (row & 7)) << 3);
-}
-
-// gelu(x) = x Phi(x) (the erf form diffusers' GEGLU uses, F.gelu) with erf by Abramowitz-Stegun 7.1.26 (|err| <= 1.5e-7,
-// far below the bf16 rounding of the result): one v_rcp + one v_exp instead of libm's branchy erff, which made the fused
-// GEGLU epilogue cost MORE than the K loop it follows (tools/ablate_gemm.py --plain: 48 of 86 us on the level-0 tile).
-// x < 0 uses q = 1 - erf directly: no cancellation in the tail.
-__device__ __forceinline__ float gelu_fast(float x) {
-    const float z = fabsf(x) * 0.7071067811865476f;
-    const float t = fast_rcp(1.f + 0.3275911f * z);
-    const float poly = t * (0.254829592f + t * (-0.284496736f + t * (1.421413741f + t * (-1.453152027f + t * 1.061405429f))));
-    const float hq = 0.5f * x * poly * fast_exp2(-z * z * 1.4426950408889634f);   // 0.5 x (1 - erf(|x| / sqrt 2))
-    return x >= 0.f ? x - hq : hq;
 }
 
 struct GemmRt {      // launch-time extras (not part of the C ABI struct)
@@ -557,10 +546,7 @@ __global__ __launch_bounds__(NWM * 128) void gemm_kernel(const leco_gemm_args p,
                     v[2 * r + 1] += bf2f((bf16_t)(rr[r] >> 16));
                 }
             }
-            if (p.act == LECO_ACT_SILU) {
-#pragma unroll
-                for (int r = 0; r < 8; ++r) v[r] = v[r] / (1.f + __expf(-v[r]));
-            }
+            apply_act(v, p.act);
             if (cp) {
                 const u32x4 o = {pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]), pack_bf2(v[4], v[5]), pack_bf2(v[6], v[7])};
                 *(u32x4*)(cp + (int64_t)m * p.ldc + n) = o;
@@ -659,10 +645,7 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(const leco_gemm_args
             v[0] += bf2f((bf16_t)(rr[0] & 0xffffu)); v[1] += bf2f((bf16_t)(rr[0] >> 16));
             v[2] += bf2f((bf16_t)(rr[1] & 0xffffu)); v[3] += bf2f((bf16_t)(rr[1] >> 16));
         }
-        if (p.act == LECO_ACT_SILU) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = v[r] / (1.f + __expf(-v[r]));
-        }
+        apply_act(v, p.act);
         if (cp) {
             u32x2 o = {pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3])};
             *(u32x2*)(cp + (int64_t)m * p.ldc + n) = o;
@@ -717,10 +700,7 @@ __global__ __launch_bounds__(256) void splitk_finish_stats_kernel(const leco_gem
                 v[0] += bf2f((bf16_t)(rr[0] & 0xffffu)); v[1] += bf2f((bf16_t)(rr[0] >> 16));
                 v[2] += bf2f((bf16_t)(rr[1] & 0xffffu)); v[3] += bf2f((bf16_t)(rr[1] >> 16));
             }
-            if (p.act == LECO_ACT_SILU) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = v[r] / (1.f + __expf(-v[r]));
-            }
+            apply_act(v, p.act);
             const u32x2 o = {pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3])};
             *(u32x2*)(cp + (int64_t)m * p.ldc + n) = o;
             if (p.c_f32) {
@@ -866,6 +846,7 @@ int validate(const leco_gemm_args& a) {
         return fail(-EINVAL, "leco_gemm: col_stats needs a bf16 output, stats_rows | m, stats_atom | n and no fused GEGLU");
     if (a.act == LECO_ACT_GEGLU && (a.n % 128 || !a.c || a.residual || a.rowbias || a.c_f32 || a.ldc % 8))
         return fail(-EINVAL, "leco_gemm: LECO_ACT_GEGLU needs n %% 128 == 0, a bf16 output and no residual / rowbias / fp32 copy");
+    if (a.act < LECO_ACT_NONE || a.act > LECO_ACT_GELU) return fail(-EINVAL, "leco_gemm: bad act %d", a.act);
     if (a.a_mode < LECO_A_PLAIN || a.a_mode > LECO_A_CONV3_TR2) return fail(-EINVAL, "leco_gemm: bad a_mode %d", a.a_mode);
     if ((a.lda0 | a.ldw | (a.a1 ? a.lda1 : 0) | (a.a_ext ? (a.ld_aext | a.ld_wext) : 0)) % 8)
         return fail(-EINVAL, "leco_gemm: operand strides must be multiples of 8 elements (16-byte DMA)");

@@ -877,6 +877,7 @@ extern "C" int leco_groupnorm_fwd(const void* x0, int64_t ld0, const void* x1, i
                                   void* y, int64_t ldy, leco_stream_t stream) {
     int rc = gn_check(c, groups, c0, x1);
     if (rc) return rc;
+    if (act != LECO_ACT_NONE && act != LECO_ACT_SILU) return fail(-EINVAL, "groupnorm: act %d unsupported (NONE / SILU)", act);
     GnSrc src{(const bf16_t*)x0, (const bf16_t*)x1, ld0, ld1, x1 ? c0 : c};
     hipStream_t s = (hipStream_t)stream;
     if (gn_use_block_kernel(gn_geom(hw, c, groups), batch, hw, c, groups)) {
@@ -913,6 +914,7 @@ extern "C" int leco_groupnorm_apply_stats(const void* x0, int64_t ld0, const voi
                                           int32_t act, float* stats, void* y, int64_t ldy, leco_stream_t stream) {
     int rc = gn_check(c, groups, c0, x1);
     if (rc) return rc;
+    if (act != LECO_ACT_NONE && act != LECO_ACT_SILU) return fail(-EINVAL, "groupnorm: act %d unsupported (NONE / SILU)", act);
     if (!cstats0 || (x1 && !cstats1)) return fail(-EINVAL, "leco_groupnorm_apply_stats: missing channel statistics");
     if (atom <= 0 || (c / groups) % atom || (x1 && c0 % atom))
         return fail(-EINVAL, "leco_groupnorm_apply_stats: atom %d must divide the group size %d and the concat split", atom, c / groups);
@@ -945,6 +947,7 @@ extern "C" int leco_groupnorm_bwd(const void* x0, int64_t ld0, const void* x1, i
                                   leco_stream_t stream) {
     int rc = gn_check(c, groups, c0, x1);
     if (rc) return rc;
+    if (act != LECO_ACT_NONE && act != LECO_ACT_SILU) return fail(-EINVAL, "groupnorm: act %d unsupported (NONE / SILU)", act);
     GnSrc src{(const bf16_t*)x0, (const bf16_t*)x1, ld0, ld1, x1 ? c0 : c};
     hipStream_t s = (hipStream_t)stream;
     if (gn_use_block_kernel(gn_geom(hw, c, groups), batch, hw, c, groups)) {

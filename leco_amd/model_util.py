@@ -9,7 +9,9 @@
   benchmark boxes);
 * single-file ``.ckpt`` / ``.safetensors`` checkpoints (LDM key layout) go through
   ``leco_amd/ckpt_convert.py`` (architecture detected from tensor shapes, key map derived from the block
-  structure; CLIP-L / OpenCLIP-H text towers rebuilt as ``transformers`` models).
+  structure; CLIP-L / OpenCLIP-H text towers rebuilt as ``transformers`` models);
+* ``native_text_encoder=True`` (opt-in) returns ``leco_amd.clip`` text encoders -- the same towers on the HIP kernels,
+  bf16 only -- instead of the ``transformers`` models; the tokenizers stay ``transformers``'.
 """
 from __future__ import annotations
 
@@ -137,9 +139,54 @@ def _load_unet_folder(path: str) -> UNet2DConditionModel:
     return unet
 
 
+NATIVE_SYNTHETIC_ERROR = ("native_text_encoder: synthetic:* models keep their hash-noise stand-in text encoders (their "
+                          "cross-attention widths are not multiples of 64, the native encoder's head width)")
+
+
+def _read_state_folder(d: str, stem: str = "model") -> dict:
+    for name in (stem + ".safetensors", "diffusion_pytorch_model.safetensors"):
+        if os.path.exists(os.path.join(d, name)):
+            from safetensors.torch import load_file
+            return load_file(os.path.join(d, name))
+    for name in ("pytorch_model.bin", "diffusion_pytorch_model.bin"):
+        if os.path.exists(os.path.join(d, name)):
+            return torch.load(os.path.join(d, name), map_location="cpu")
+    raise FileNotFoundError(f"{d}: no {stem}.safetensors / pytorch_model.bin")
+
+
+def load_native_text_encoder(folder: str, num_hidden_layers: Optional[int] = None, projection: bool = False,
+                             weight_dtype: torch.dtype = torch.bfloat16):
+    """A diffusers ``text_encoder`` folder (``config.json`` + ``model.safetensors`` / ``pytorch_model.bin``) as a
+    `leco_amd.clip` model; ``num_hidden_layers`` trims the tower (clip_skip / the v2 penultimate layer): the tensors of
+    the dropped layers are left out, every other missing or unexpected key is a KeyError naming it.  ``weight_dtype`` is
+    only the dtype the parameters are held (and the outputs returned) in: the encoder computes in bf16."""
+    from . import clip as CL
+    over = {} if num_hidden_layers is None else {"num_hidden_layers": num_hidden_layers}
+    cfg = CL.CLIPTextConfig.from_json(os.path.join(folder, "config.json"), **over)
+    sd = _native_clip_state(_read_state_folder(folder), cfg.num_hidden_layers, projection)
+    model = (CL.CLIPTextModelWithProjection if projection else CL.CLIPTextModel)(cfg)
+    model.load_state_dict(sd)
+    return model.to(weight_dtype)
+
+
+def _native_clip_state(sd: dict, layers: int, projection: bool) -> dict:
+    """HF text-encoder state dict -> what the trimmed native tower holds: the ``text_model.`` prefix restored where a
+    newer ``transformers`` saved without it, layers >= `layers` and (without a projection head) ``text_projection`` dropped."""
+    if not any(k.startswith("text_model.") for k in sd):
+        sd = {(k if k.startswith("text_projection.") else "text_model." + k): v for k, v in sd.items()}
+    out = {}
+    for k, v in sd.items():
+        if k.startswith("text_model.encoder.layers.") and int(k.split(".")[3]) >= layers:
+            continue
+        if k.startswith("text_projection.") and not projection:
+            continue
+        out[k] = v
+    return out
+
+
 def load_diffusers_model(path: str, v2: bool = False, clip_skip: Optional[int] = None,
-                         weight_dtype: torch.dtype = torch.float32):
-    from transformers import CLIPTextModel, CLIPTokenizer
+                         weight_dtype: torch.dtype = torch.float32, native_text_encoder: bool = False):
+    from transformers import CLIPTokenizer
     tokenizer = CLIPTokenizer.from_pretrained(path, subfolder="tokenizer")
     full = 24 if v2 else 12             # the released checkpoints (model_util.py:43-49, 58-61) ...
     try:                                # ... or whatever the folder's own config says (reduced test models)
@@ -149,8 +196,12 @@ def load_diffusers_model(path: str, v2: bool = False, clip_skip: Optional[int] =
         pass
     default_layers = full - 1 if v2 else full   # v2: penultimate layer (model_util.py:43-49)
     nl = full - (clip_skip - 1) if clip_skip is not None else default_layers
-    text_encoder = CLIPTextModel.from_pretrained(path, subfolder="text_encoder", num_hidden_layers=nl,
-                                                 torch_dtype=weight_dtype)
+    if native_text_encoder:
+        text_encoder = load_native_text_encoder(os.path.join(path, "text_encoder"), nl, weight_dtype=weight_dtype)
+    else:
+        from transformers import CLIPTextModel
+        text_encoder = CLIPTextModel.from_pretrained(path, subfolder="text_encoder", num_hidden_layers=nl,
+                                                     torch_dtype=weight_dtype)
     unet = _load_unet_folder(os.path.join(path, "unet")).to(weight_dtype)
     return tokenizer, text_encoder, unet
 
@@ -178,10 +229,11 @@ def _find_tokenizer_dir(ckpt_path: str) -> str:
 
 
 def load_checkpoint_model(checkpoint_path: str, v2: bool = False, clip_skip: Optional[int] = None,
-                          weight_dtype: torch.dtype = torch.float32):
+                          weight_dtype: torch.dtype = torch.float32, native_text_encoder: bool = False):
     """model_util.py:75-101 (`StableDiffusionPipeline.from_single_file`): tokenizer, text encoder and UNet of a
-    `.ckpt` / `.safetensors` file in the LDM key layout; the VAE is never touched."""
-    from transformers import CLIPTextConfig, CLIPTextModel, CLIPTokenizer
+    `.ckpt` / `.safetensors` file in the LDM key layout; the VAE is never touched.  ``native_text_encoder``: the converted
+    state dict goes straight into a `leco_amd.clip.CLIPTextModel` (no ``transformers`` model object is built)."""
+    from transformers import CLIPTokenizer
     from . import ckpt_convert as cc
     tokenizer_dir = _find_tokenizer_dir(checkpoint_path)                # fail fast: nothing below can fetch it
     sd = cc.read_checkpoint(checkpoint_path)
@@ -208,6 +260,18 @@ def load_checkpoint_model(checkpoint_path: str, v2: bool = False, clip_skip: Opt
                 num_attention_heads=max(1, hidden // 64),
                 max_position_embeddings=int(te_sd["text_model.embeddings.position_embedding.weight"].shape[0]))
     nl = full - (clip_skip - 1) if clip_skip is not None else full - drop_last   # model_util.py:92-96
+    if native_text_encoder:
+        from . import clip as CL
+        ncfg = CL.CLIPTextConfig(num_hidden_layers=nl, bos_token_id=tcfg["vocab_size"] - 2, eos_token_id=tcfg["vocab_size"] - 1,
+                                 **tcfg)
+        text_encoder = CL.CLIPTextModel(ncfg)
+        try:
+            text_encoder.load_state_dict(_native_clip_state(te_sd, nl, False))
+        except KeyError as e:
+            raise KeyError(f"{checkpoint_path}: {e.args[0]}") from None
+        tokenizer = CLIPTokenizer.from_pretrained(tokenizer_dir)
+        return tokenizer, text_encoder.to(weight_dtype), unet.to(weight_dtype)
+    from transformers import CLIPTextConfig, CLIPTextModel
     # CLIP's BPE vocabulary ends with <|startoftext|>, <|endoftext|> (49406 / 49407); pooling looks for the latter
     text_encoder = CLIPTextModel(CLIPTextConfig(num_hidden_layers=nl, bos_token_id=tcfg["vocab_size"] - 2,
                                                 eos_token_id=tcfg["vocab_size"] - 1, **tcfg))
@@ -286,14 +350,18 @@ def load_vae(path: str, precision: str = "bfloat16", scaling_factor: Optional[fl
 
 
 def load_models(pretrained_model_name_or_path: str, scheduler_name: str, v2: bool = False, v_pred: bool = False,
-                weight_dtype: torch.dtype = torch.float32):
+                weight_dtype: torch.dtype = torch.float32, native_text_encoder: bool = False):
     p = pretrained_model_name_or_path
     if p.startswith("synthetic:"):
+        if native_text_encoder:
+            raise ValueError(NATIVE_SYNTHETIC_ERROR)
         tokenizer, text_encoder, unet = load_synthetic_model(p.split(":", 1)[1])
     elif p.endswith(".ckpt") or p.endswith(".safetensors"):
-        tokenizer, text_encoder, unet = load_checkpoint_model(p, v2=v2, weight_dtype=weight_dtype)
+        tokenizer, text_encoder, unet = load_checkpoint_model(p, v2=v2, weight_dtype=weight_dtype,
+                                                              native_text_encoder=native_text_encoder)
     elif os.path.isdir(p):
-        tokenizer, text_encoder, unet = load_diffusers_model(p, v2=v2, weight_dtype=weight_dtype)
+        tokenizer, text_encoder, unet = load_diffusers_model(p, v2=v2, weight_dtype=weight_dtype,
+                                                             native_text_encoder=native_text_encoder)
     else:
         raise FileNotFoundError(f"{p}: not a local diffusers folder (no network access on this system); "
                                 f"use a local path or synthetic:<sd15|sd21|sdxl|tiny>")
@@ -301,9 +369,12 @@ def load_models(pretrained_model_name_or_path: str, scheduler_name: str, v2: boo
     return tokenizer, text_encoder, unet, scheduler
 
 
-def load_models_xl(pretrained_model_name_or_path: str, scheduler_name: str, weight_dtype: torch.dtype = torch.float32):
+def load_models_xl(pretrained_model_name_or_path: str, scheduler_name: str, weight_dtype: torch.dtype = torch.float32,
+                   native_text_encoder: bool = False):
     """model_util.py:205-227: returns ([tokenizer, tokenizer_2], [text_encoder, text_encoder_2], unet, scheduler)."""
     p = pretrained_model_name_or_path
+    if native_text_encoder and p.startswith("synthetic:"):
+        raise ValueError(NATIVE_SYNTHETIC_ERROR)
     if p.startswith("synthetic:"):
         kind = p.split(":", 1)[1]
         cfg = tiny_xl_config() if kind in ("tiny_xl", "tinyxl") else SYNTHETIC[kind]()
@@ -319,9 +390,14 @@ def load_models_xl(pretrained_model_name_or_path: str, scheduler_name: str, weig
         from transformers import CLIPTextModel, CLIPTextModelWithProjection, CLIPTokenizer
         tokenizers = [CLIPTokenizer.from_pretrained(p, subfolder="tokenizer"),
                       CLIPTokenizer.from_pretrained(p, subfolder="tokenizer_2", pad_token_id=0)]
-        text_encoders = [CLIPTextModel.from_pretrained(p, subfolder="text_encoder", torch_dtype=weight_dtype),
-                         CLIPTextModelWithProjection.from_pretrained(p, subfolder="text_encoder_2",
-                                                                     torch_dtype=weight_dtype)]
+        if native_text_encoder:
+            text_encoders = [load_native_text_encoder(os.path.join(p, "text_encoder"), weight_dtype=weight_dtype),
+                             load_native_text_encoder(os.path.join(p, "text_encoder_2"), projection=True,
+                                                      weight_dtype=weight_dtype)]
+        else:
+            text_encoders = [CLIPTextModel.from_pretrained(p, subfolder="text_encoder", torch_dtype=weight_dtype),
+                             CLIPTextModelWithProjection.from_pretrained(p, subfolder="text_encoder_2",
+                                                                         torch_dtype=weight_dtype)]
         unet = _load_unet_folder(os.path.join(p, "unet")).to(weight_dtype)
     else:
         raise FileNotFoundError(f"{p}: not a local diffusers folder; use a local path or synthetic:<sdxl|tiny_xl>")

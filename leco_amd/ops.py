@@ -29,6 +29,8 @@ _SIGS = {
     "leco_attention_bwd": [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64,
                            _vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64,
                            _i32, _i32, _i32, _i32, _i32, _f32, _vp],
+    "leco_attention_causal_fwd": [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _f32, _vp],
+    "leco_embed_rows": [_vp, _i64, _i32, _vp, _vp, _i64, _i32, _vp, _i64, _i32, _i32, _vp],
     "leco_gemm_ex": [C.POINTER(GemmArgs), _i32, _i32, _vp, _i64, _vp],
     "leco_geglu_fwd": [_vp, _i64, _vp, _i64, _i32, _i32, _vp],
     "leco_geglu_bwd": [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp],
@@ -224,6 +226,45 @@ def attention_bwd(q, ldq, bsq, k, ldk, bsk, v, ldv, bsv, o, ldo, bso, do, lddo, 
     return Op("leco_attention_bwd", (q, ldq, bsq, k, ldk, bsk, v, ldv, bsv, o, ldo, bso, do, lddo, bsdo,
                                      ptr(lse), ptr(delta), dq, lddq, bsdq, dk, lddk, bsdk, dv, lddv,
                                      bsdv, batch, heads, sq, skv, d, scale))
+
+
+CAUSAL_ATTN_MAX_S = 128      # LECO_CAUSAL_ATTN_MAX_S
+
+
+def attention_causal_fwd(q, ldq, bsq, k, ldk, bsk, v, ldv, bsv, o, ldo, bso, batch, heads, s, d, scale, keep=None) -> Op:
+    """softmax(q k^T scale + causal) v per (batch, head); q, k, v, o are raw device addresses (column views of a fused
+    q|k|v buffer can be passed), head dim 64, s <= CAUSAL_ATTN_MAX_S."""
+    return Op("leco_attention_causal_fwd", (q, ldq, bsq, k, ldk, bsk, v, ldv, bsv, o, ldo, bso, batch, heads, s, d, scale),
+              keep=keep)
+
+
+def check_row_ids(ids: torch.Tensor, rows: int, what: str = "ids") -> torch.Tensor:
+    """The HOST-side index check of `embed_rows`: ``ids`` (any integer tensor) as contiguous int32 on the host, or
+    IndexError when an entry lies outside [0, rows) -- before anything is launched."""
+    t = torch.as_tensor(ids)
+    if t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise TypeError(f"{what}: expected an integer tensor, got {t.dtype}")
+    t = t.detach().to("cpu", torch.int64).reshape(-1)
+    if t.numel() and (int(t.min()) < 0 or int(t.max()) >= rows):
+        bad = int(t[(t < 0) | (t >= rows)][0])
+        raise IndexError(f"{what}: index {bad} is out of range for a table of {rows} rows")
+    return t.to(torch.int32).contiguous()
+
+
+def embed_rows(table, ldt, rows, idx, pos, ldp, period, out, ldo, n, c, keep=None) -> Op:
+    """out[i] = table[idx[i]] (+ pos[i % period]) on bf16 rows; ``idx``: DEVICE int32 [n] whose values went through
+    `check_row_ids` on the host."""
+    return Op("leco_embed_rows", (ptr(table), ldt, rows, ptr(idx), ptr(pos), ldp, period, ptr(out), ldo, n, c),
+              keep=(table, idx, pos, out, keep))
+
+
+def embed_rows_checked(table: torch.Tensor, ids: torch.Tensor, pos: Optional[torch.Tensor], period: int,
+                       out: torch.Tensor) -> Op:
+    """`embed_rows` on whole tensors: validates ``ids`` on the host (IndexError) and moves them to the table's device."""
+    rows, c = table.shape
+    idx = check_row_ids(ids, rows).to(table.device)
+    return embed_rows(table, table.stride(0), rows, idx, pos, 0 if pos is None else pos.stride(0), period, out, out.stride(0),
+                      idx.numel(), c)
 
 
 def geglu_fwd(u, ldu, y, ldy, m, f) -> Op:

@@ -686,7 +686,7 @@ def _parse_optimizer_args(s: str) -> dict:
 def train(config: RootConfig, prompts: List[PromptSettings], device: Optional[torch.device] = None,
           use_graphs: bool = True, progress: bool = True, xl: bool = False, resume_from: Optional[str] = None,
           save_state: bool = False, stop_after: Optional[int] = None, strict_reference: bool = False,
-          dedup: Optional[bool] = None):
+          dedup: Optional[bool] = None, native_text_encoder: bool = False):
     """Reference entry point ``train(config, prompts)`` (train_lora.py:34; ``xl=True``: train_lora_xl.py:40).
     Extra keyword arguments only select the device and execution mode, and the resume extension:
     ``save_state`` writes ``{save.name}_state.pt`` next to every saved LoRA, ``resume_from`` continues from one
@@ -694,7 +694,8 @@ def train(config: RootConfig, prompts: List[PromptSettings], device: Optional[to
     ``strict_reference`` keeps the LoRA parameters and the optimizer state in ``train.precision`` like the reference
     (`StrictReferenceOptimizer`) instead of fp32 masters.  ``dedup`` (default: on unless ``strict_reference`` or
     LECO_DEDUP=0): the de-duplicated pass structure of `FusedStep` -- the guidance-1 passes run on the conditional samples
-    only and identical prompts once; same objective, ~10 % fewer FLOPs per step at the reference's prompt settings."""
+    only and identical prompts once; same objective, ~10 % fewer FLOPs per step at the reference's prompt settings.
+    ``native_text_encoder``: the prompts are encoded by `leco_amd.clip` instead of the ``transformers`` models (bf16 only)."""
     if dedup is None:
         dedup = not strict_reference and os.environ.get("LECO_DEDUP", "1") not in ("", "0")
     rank, world, local = init_distributed()
@@ -724,10 +725,14 @@ def train(config: RootConfig, prompts: List[PromptSettings], device: Optional[to
     if weight_dtype == torch.float16:
         print("note: train.precision=float16 is computed in the fp32 mode (there are no fp16 kernels; bf16 would be narrower "
               "than requested); only the saved LoRA is fp16.  Use bfloat16 for the fast MFMA path.")
+    if native_text_encoder and compute_dtype != torch.bfloat16:
+        raise NotImplementedError(f"--native_text_encoder: the native CLIP text encoder is bf16-only, train.precision "
+                                  f"{config.train.precision!r} runs in the fp32 mode; drop the flag or use bfloat16")
 
     if xl:
         tokenizers, text_encoders, unet, noise_scheduler = model_util.load_models_xl(
-            config.pretrained_model.name_or_path, scheduler_name=config.train.noise_scheduler)
+            config.pretrained_model.name_or_path, scheduler_name=config.train.noise_scheduler,
+            native_text_encoder=native_text_encoder)
         for text_encoder in text_encoders:
             text_encoder.to(device, dtype=compute_dtype)
             text_encoder.eval()
@@ -735,7 +740,7 @@ def train(config: RootConfig, prompts: List[PromptSettings], device: Optional[to
     else:
         tokenizer, text_encoder, unet, noise_scheduler = model_util.load_models(
             config.pretrained_model.name_or_path, scheduler_name=config.train.noise_scheduler,
-            v2=config.pretrained_model.v2, v_pred=config.pretrained_model.v_pred)
+            v2=config.pretrained_model.v2, v_pred=config.pretrained_model.v_pred, native_text_encoder=native_text_encoder)
         text_encoder.to(device, dtype=compute_dtype)
         text_encoder.eval()
     unet.to(device, dtype=compute_dtype)
@@ -912,7 +917,8 @@ def main(args, xl: bool = False):
     try:
         train(config, prompts, xl=xl, resume_from=getattr(args, "resume", None),
               save_state=bool(getattr(args, "save_state", False)),
-              strict_reference=bool(getattr(args, "strict_reference", False)))
+              strict_reference=bool(getattr(args, "strict_reference", False)),
+              native_text_encoder=bool(getattr(args, "native_text_encoder", False)))
         failed = False
     finally:      # every rank, also the one that is on its way out with an exception
         shutdown_distributed(failed=failed)

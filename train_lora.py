@@ -15,4 +15,6 @@ if __name__ == "__main__":
     parser.add_argument("--resume", default=None, help="continue from a {save.name}_state.pt of the same config")
     parser.add_argument("--strict_reference", action="store_true",
                         help="LoRA parameters and optimizer state in train.precision, like the reference (default: fp32 masters)")
+    parser.add_argument("--native_text_encoder", action="store_true",
+                        help="encode the prompts with the native CLIP text encoder (leco_amd.clip, bf16 only) instead of transformers")
     main(parser.parse_args())

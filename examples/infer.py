@@ -5,9 +5,11 @@
 `get_initial_latents` -> `train_util.diffusion` (DDIM, classifier-free guidance) through the HIP UNet, optionally with a
 trained LoRA applied (`--lora out/x_last.safetensors`, the file `train_lora.py` writes).  The latents go to a safetensors
 file (`--out`); with `--image PATH` they are decoded by the HIP VAE decoder (`leco_amd/vae.py`) and saved as a PNG, as
-the reference's `test/infer_xl.py:136-154` does for SDXL.
+the reference's `test/infer_xl.py:136-154` does for SDXL.  With `--init_image PNG --strength S` the run is img2img: the
+image is encoded by the HIP VAE encoder, noised to the timestep `S` selects, and only the rest of the schedule is run.
 
     python examples/infer.py --model synthetic:tiny --height 128 --width 128 --steps 4 --image out.png
+    python examples/infer.py --model synthetic:tiny --height 128 --width 128 --steps 4 --init_image out.png --strength 0.5 --image out2.png
     python examples/infer.py --model /models/sd21 --v2 --v_pred --height 768 --width 768 --lora output/x_last.safetensors --image x.png
 """
 import argparse
@@ -21,16 +23,21 @@ import torch
 from safetensors.torch import save_file
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
+sys.path[:0] = [os.path.dirname(HERE), HERE]
 from leco_amd import model_util, train_util  # noqa: E402
 from leco_amd.lora import LoRANetwork  # noqa: E402
+from _img2img import init_latents  # noqa: E402
 
 
-def _write_image(*a, **k):
+def _infer_xl():
     spec = importlib.util.spec_from_file_location("infer_xl", os.path.join(HERE, "infer_xl.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    return mod.write_image(*a, **k)
+    return mod
+
+
+def _write_image(*a, **k):
+    return _infer_xl().write_image(*a, **k)
 
 
 @torch.no_grad()
@@ -54,11 +61,15 @@ def main(argv=None):
     ap.add_argument("--out", default="latents.safetensors")
     ap.add_argument("--image", default=None, help="decode the latents with the VAE and write this PNG")
     ap.add_argument("--vae", default=None, help="VAE for --image (default: the model's vae/ folder, or its synthetic VAE)")
+    ap.add_argument("--init_image", default=None, help="img2img: start from this PNG (its size must be --height x --width)")
+    ap.add_argument("--strength", type=float, default=0.6, help="img2img: 0 < S <= 1, the share of the schedule that is run")
     ap.add_argument("--native_text_encoder", action="store_true",
                     help="encode the prompts with the native CLIP text encoder (leco_amd.clip, bf16 only) instead of transformers")
     args = ap.parse_args(argv)
     dev = torch.device(args.device)
     dtype = torch.bfloat16
+    if args.init_image and not 0.0 < args.strength <= 1.0:
+        raise ValueError(f"--strength must be in (0, 1], got {args.strength}")
     tokenizer, text_encoder, unet, sched = model_util.load_models(args.model, scheduler_name="ddim", v2=args.v2, v_pred=args.v_pred,
                                                                   native_text_encoder=args.native_text_encoder)
     text_encoder.to(dev, dtype=dtype)
@@ -78,9 +89,14 @@ def main(argv=None):
     text_embeds = train_util.concat_embeddings(neg, pos, 1)
     sched.set_timesteps(args.steps, device=dev)
     torch.manual_seed(args.seed)
-    latents = train_util.get_initial_latents(sched, 1, args.height, args.width, 1).to(dev, dtype=dtype)
+    t_start = 0
+    if args.init_image:
+        latents, t_start = init_latents(args, sched, dev, use_graphs=unet.use_graphs)
+        latents = latents.to(dtype)
+    else:
+        latents = train_util.get_initial_latents(sched, 1, args.height, args.width, 1).to(dev, dtype=dtype)
     with (network if network is not None else contextlib.nullcontext()):
-        latents = train_util.diffusion(unet, sched, latents, text_embeds, total_timesteps=args.steps, start_timesteps=0,
+        latents = train_util.diffusion(unet, sched, latents, text_embeds, total_timesteps=args.steps, start_timesteps=t_start,
                                        guidance_scale=args.guidance_scale)
     save_file({"latents": latents.float().cpu().contiguous()}, args.out,
               {"prompt": args.prompt, "steps": str(args.steps), "guidance_scale": str(args.guidance_scale)})

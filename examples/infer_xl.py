@@ -11,7 +11,13 @@ The latents are written to a safetensors file (`--out`).  With `--image PATH` th
 (`leco_amd/vae.py`; `--vae` names the VAE: a diffusers folder, a single-file checkpoint or `synthetic:...`; default: the
 model's own `vae/` folder, or the synthetic VAE of a synthetic model).  Without `--image` nothing about the VAE is loaded.
 
+With `--init_image PNG --strength S` (0 < S <= 1, default 0.6) the run is img2img: the PNG (its size must be `--height` x
+`--width`) is encoded by the HIP VAE encoder (`encode_to_latents`, the same `--vae`), noised with `scheduler.add_noise` to
+`timesteps[steps - min(int(steps * S), steps)]`, and the rest of the schedule is run -- with and without `--lora`, so one
+can see what a trained LoRA does to a given picture.
+
     python examples/infer_xl.py --model synthetic:tiny_xl --height 128 --width 128 --steps 4 --image out.png
+    python examples/infer_xl.py --model synthetic:tiny_xl --height 128 --width 128 --steps 4 --init_image out.png --strength 0.5 --image out2.png
     python examples/infer_xl.py --model /models/sdxl-base --lora output/x_last.safetensors --prompt "a photo of lemonade" --image lemonade.png
 """
 import argparse
@@ -23,9 +29,11 @@ import sys
 import torch
 from safetensors.torch import save_file
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path[:0] = [os.path.dirname(HERE), HERE]
 from leco_amd import model_util, train_util  # noqa: E402
 from leco_amd.lora import LoRANetwork  # noqa: E402
+from _img2img import init_latents  # noqa: E402
 
 SDXL_NOISE_OFFSET = 0.0357      # test/infer_xl.py:27
 
@@ -49,11 +57,15 @@ def main(argv=None):
     ap.add_argument("--out", default="latents.safetensors")
     ap.add_argument("--image", default=None, help="decode the latents with the VAE and write this PNG")
     ap.add_argument("--vae", default=None, help="VAE for --image (default: the model's vae/ folder, or its synthetic VAE)")
+    ap.add_argument("--init_image", default=None, help="img2img: start from this PNG (its size must be --height x --width)")
+    ap.add_argument("--strength", type=float, default=0.6, help="img2img: 0 < S <= 1, the share of the schedule that is run")
     ap.add_argument("--native_text_encoder", action="store_true",
                     help="encode the prompts with the native CLIP text encoder (leco_amd.clip, bf16 only) instead of transformers")
     args = ap.parse_args(argv)
     dev = torch.device(args.device)
     dtype = torch.bfloat16
+    if args.init_image and not 0.0 < args.strength <= 1.0:
+        raise ValueError(f"--strength must be in (0, 1], got {args.strength}")
     tokenizers, text_encoders, unet, sched = model_util.load_models_xl(args.model, scheduler_name="ddim",
                                                                         native_text_encoder=args.native_text_encoder)
     for te in text_encoders:
@@ -77,12 +89,17 @@ def main(argv=None):
     add_time_ids = train_util.concat_embeddings(add_time_ids, add_time_ids, 1)
     sched.set_timesteps(args.steps, device=dev)
     torch.manual_seed(args.seed)
-    latents = train_util.get_initial_latents(sched, 1, args.height, args.width, 1)
-    latents = train_util.apply_noise_offset(latents * sched.init_noise_sigma, SDXL_NOISE_OFFSET).to(dev, dtype=dtype)
+    t_start = 0
+    if args.init_image:
+        latents, t_start = init_latents(args, sched, dev, use_graphs=unet.use_graphs)
+        latents = latents.to(dtype)
+    else:
+        latents = train_util.get_initial_latents(sched, 1, args.height, args.width, 1)
+        latents = train_util.apply_noise_offset(latents * sched.init_noise_sigma, SDXL_NOISE_OFFSET).to(dev, dtype=dtype)
     with (network if network is not None else contextlib.nullcontext()):
         latents = train_util.diffusion_xl(unet, sched, latents, text_embeddings=text_embeds,
                                           add_text_embeddings=add_text_embeds, add_time_ids=add_time_ids,
-                                          total_timesteps=args.steps, start_timesteps=0, guidance_scale=args.guidance_scale)
+                                          total_timesteps=args.steps, start_timesteps=t_start, guidance_scale=args.guidance_scale)
     save_file({"latents": latents.float().cpu().contiguous()}, args.out,
               {"prompt": args.prompt, "steps": str(args.steps), "guidance_scale": str(args.guidance_scale)})
     print(f"Done. latents {tuple(latents.shape)} -> {args.out}")

@@ -42,7 +42,13 @@ enum {
     LECO_A_CONV3_S1 = 1,   /* 3x3 pad 1 stride 1 on NHWC input, K = 9*Cin, k = tap*Cin + c */
     LECO_A_CONV3_S2 = 2,   /* 3x3 pad 1 stride 2 (Downsample2D) */
     LECO_A_CONV3_UP2 = 3,  /* 3x3 pad 1 on the nearest-2x upsampled input (Upsample2D) */
-    LECO_A_CONV3_TR2 = 4   /* transposed stride-2 gather: dgrad of LECO_A_CONV3_S2 */
+    LECO_A_CONV3_TR2 = 4,  /* transposed stride-2 gather: dgrad of LECO_A_CONV3_S2 */
+    /* 3x3 stride 2 with padding on the bottom / right only (diffusers Downsample2D(padding=0): F.pad(x, (0,1,0,1)) then a
+     * pad-0 conv, the VAE encoder's downsample): tap (kh, kw) of output (y, x) reads input (2y + kh, 2x + kw), zero past
+     * the last row / column.  h_in, w_in even, h_out = h_in / 2, w_out = w_in / 2, else -EINVAL.  leco_gemm (every tile of the
+     * implicit-GEMM kernel, split-K, column statistics) only: leco_f32_gemm, leco_lora_wgrad_conv and the patch-staged
+     * convolution refuse it by name. */
+    LECO_A_CONV3_S2_PAD01 = 5
 };
 /* LECO_ACT_GEGLU (leco_gemm only): the GEMM is the GEGLU input projection (diffusers GEGLU.proj, N = 2F) with its
  * weight / bias / w_ext ROWS interleaved in blocks of 64 -- row 128 j + r holds value row 64 j + r (r < 64) or gate
@@ -301,6 +307,22 @@ int leco_latent_affine(const float* x, const float* w, const float* bias, void* 
  * pre-rounding result, and img: uint8 NHWC (batch,h,w,3) = floor(clamp(y / 2 + 0.5, 0, 1) * 255 + 0.5). */
 int leco_conv_out_rgb(const void* x, const void* w, const float* bias, float* y, void* img, int32_t batch, int32_t h,
                       int32_t wd, int32_t c, leco_stream_t stream);
+/* VAE encoder conv_in: 3x3 pad 1 from a 3-channel image to channels-last bf16 [batch*h*w][cout], cout % 32 == 0.  The image
+ * comes from exactly one of x: fp32 NCHW (batch,3,h,w), values in [-1, 1], and img: uint8 NHWC (batch,h,w,3), meaning the
+ * fp32 number (float)p / 127.5f - 1.f, so that img and x = img / 127.5 - 1 give the same bits (the other NULL; both or
+ * neither: -EINVAL).  w fp32 [cout][3][3][3] (the Conv2d layout: channel, kh, kw), bias
+ * fp32 [cout].  fp32 accuracy before the single bf16 rounding of the output; padding taps are exactly 0 in the normalised
+ * space. */
+int leco_conv_in_rgb(const float* x, const void* img, const float* w, const float* bias, void* y, int32_t batch, int32_t h,
+                     int32_t wd, int32_t cout, leco_stream_t stream);
+/* VAE encoder exit: channels-last bf16 [batch*h*w][c] (c % 32 == 0) -> 3x3 pad 1 conv to 8 channels (w bf16 [8][3][3][c], bias
+ * fp32 [8]) -> quant_conv as an fp32 8x8 matrix qw [out][in] + bias qb [8] on the fp32 accumulators.  Writes either or both
+ * (not neither) of moments: fp32 NCHW (batch,8,h,w) = [mean | logvar], and latents: fp32 NCHW (batch,4,h,w) =
+ * scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * noise), noise fp32 NCHW (batch,4,h,w); noise == NULL gives the mode,
+ * scale * mean. */
+int leco_conv_out_moments(const void* x, const void* w, const float* bias, const float* qw, const float* qb, const float* noise,
+                          float* moments, float* latents, float scale, int32_t batch, int32_t h, int32_t wd, int32_t c,
+                          leco_stream_t stream);
 /* diffusers Timesteps(flip_sin_to_cos=True, freq_shift=0): out[i] = [cos | sin](t_i * f), bf16
  * [n][dim]; t_i = t_table[*idx + i*t_stride] (idx may be NULL => 0): the timestep is read on
  * the device so a captured graph can be replayed for every denoising step. */

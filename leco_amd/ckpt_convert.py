@@ -232,10 +232,36 @@ def vae_decoder_levels(sd: Dict[str, torch.Tensor]) -> int:
     return max(idx) + 1
 
 
-def _ldm_vae_key(k: str, levels: int) -> Optional[str]:
-    """One LDM decoder parameter name -> the diffusers name (None: not a decoder parameter: encoder, quant_conv, loss)."""
+def _ldm_vae_encoder_key(k: str) -> str:
+    """One LDM `encoder.*` parameter name -> the diffusers name (the level order is the same on this side)."""
+    k = k.replace(".nin_shortcut.", ".conv_shortcut.")
+    m = re.match(r"encoder\.mid\.block_(\d)\.(.+)", k)
+    if m:
+        return f"encoder.mid_block.resnets.{int(m.group(1)) - 1}.{m.group(2)}"
+    m = re.match(r"encoder\.mid\.attn_1\.(norm|q|k|v|proj_out)\.(weight|bias)", k)
+    if m:
+        return f"encoder.mid_block.attentions.0.{_VAE_ATTN[m.group(1)]}.{m.group(2)}"
+    m = re.match(r"encoder\.down\.(\d+)\.block\.(\d+)\.(.+)", k)
+    if m:
+        return f"encoder.down_blocks.{m.group(1)}.resnets.{m.group(2)}.{m.group(3)}"
+    m = re.match(r"encoder\.down\.(\d+)\.downsample\.conv\.(.+)", k)
+    if m:
+        return f"encoder.down_blocks.{m.group(1)}.downsamplers.0.conv.{m.group(2)}"
+    m = re.match(r"encoder\.norm_out\.(.+)", k)
+    if m:
+        return f"encoder.conv_norm_out.{m.group(1)}"
+    return k          # encoder.conv_in / encoder.conv_out keep their names; anything else surfaces as an unexpected key
+
+
+def _ldm_vae_key(k: str, levels: int, encoder: bool = False) -> Optional[str]:
+    """One LDM VAE parameter name -> the diffusers name (None: not a parameter of the halves that are built: the loss, and
+    without `encoder` the encoder and quant_conv)."""
     if k.startswith("post_quant_conv."):
         return k
+    if encoder and k.startswith("quant_conv."):
+        return k
+    if encoder and k.startswith("encoder."):
+        return _ldm_vae_encoder_key(k)
     if not k.startswith("decoder."):
         return None
     k = k.replace(".nin_shortcut.", ".conv_shortcut.")
@@ -257,15 +283,16 @@ def _ldm_vae_key(k: str, levels: int) -> Optional[str]:
     return k          # decoder.conv_in / decoder.conv_out keep their names; anything else surfaces as an unexpected key
 
 
-def convert_ldm_vae(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+def convert_ldm_vae(sd: Dict[str, torch.Tensor], encoder: bool = False) -> Dict[str, torch.Tensor]:
     """`first_stage_model.*` entries of an LDM checkpoint -> diffusers-named state dict of the DECODER half
-    (post_quant_conv + decoder); the 1x1-conv attention weights [C][C][1][1] become Linear weights [C][C]."""
+    (post_quant_conv + decoder) and, with `encoder`, the encoder half (encoder + quant_conv); the 1x1-conv attention weights
+    [C][C][1][1] become Linear weights [C][C]."""
     levels = vae_decoder_levels(sd)
     out = {}
     for k, v in sd.items():
         if not k.startswith(VAE_PREFIX):
             continue
-        nk = _ldm_vae_key(k[len(VAE_PREFIX):], levels)
+        nk = _ldm_vae_key(k[len(VAE_PREFIX):], levels, encoder)
         if nk is None:
             continue
         if ".attentions.0.to_" in nk and nk.endswith(".weight") and v.ndim == 4:
@@ -274,14 +301,15 @@ def convert_ldm_vae(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     return out
 
 
-def normalise_vae_keys(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
-    """A diffusers VAE state dict restricted to the decoder half, with the older attention spelling
-    (`query / key / value / proj_attn`) renamed to `to_q / to_k / to_v / to_out.0`."""
+def normalise_vae_keys(sd: Dict[str, torch.Tensor], encoder: bool = False) -> Dict[str, torch.Tensor]:
+    """A diffusers VAE state dict restricted to the decoder half (with `encoder`: both halves), with the older attention
+    spelling (`query / key / value / proj_attn`) renamed to `to_q / to_k / to_v / to_out.0`."""
     out = {}
+    keep = ("decoder.", "post_quant_conv.") + (("encoder.", "quant_conv.") if encoder else ())
     for k, v in sd.items():
-        if not (k.startswith("decoder.") or k.startswith("post_quant_conv.")):
+        if not k.startswith(keep):
             continue
-        m = re.match(r"(decoder\.mid_block\.attentions\.\d+)\.(query|key|value|proj_attn)\.(weight|bias)", k)
+        m = re.match(r"((?:decoder|encoder)\.mid_block\.attentions\.\d+)\.(query|key|value|proj_attn)\.(weight|bias)", k)
         if m:
             k = f"{m.group(1)}.{_VAE_ATTN_OLD[m.group(2)]}.{m.group(3)}"
         if ".attentions." in k and ".to_" in k and k.endswith(".weight") and v.ndim == 4:

@@ -392,6 +392,174 @@ __global__ __launch_bounds__(256) void conv_out_rgb_kernel(const bf16_t* x, cons
     }
 }
 
+// ---- VAE encoder conv_in: 3x3 pad 1 from a 3-channel image to channels-last bf16 [batch*h*w][Cout] ------------------------
+// The image is fp32 NCHW in [-1, 1] (x) or 8-bit NHWC (img, meaning p / 127.5 - 1).  A [pixels][27] x [27][Cout] GEMM whose
+// K fits ONE 32-wide MFMA k-step; the launch writes Cout * 2 bytes per pixel against 3..12 read (67 MB vs 0.8 MB at 512^2), so
+// it is laid out for its stores: a wave owns 16 consecutive pixels and every output channel of them -- one contiguous
+// 16 * Cout * 2 byte span -- and the weight-row order of a fragment PAIR is permuted (row 4 fg + r of fragment j is channel
+// 32 P + 8 fg + 4 j + r) so that a lane ends up with 8 consecutive channels of its pixel: one 16-byte store, the 4 lanes fg of
+// a pixel a full 64-byte segment.  Weights stay in registers, fp32 split into bf16 hi + lo (as conv_in_mfma_kernel); the
+// image value is split the same way (hi*hi + lo*hi + hi*lo: ~2^-17 relative before the single bf16 rounding).  An 8-bit pixel
+// p means the fp32 number (float)p / 127.5f - 1.f -- what `img.float() / 127.5 - 1` gives -- looked up, already split, in a
+// 256-entry LDS table, so the two inputs describing one image give the same bits; a padding tap is 0 in that normalised space.
+constexpr int RGB_PAIRS = 4;       // 32-channel pairs per pass: blockIdx.y walks Cout in steps of 128
+__global__ __launch_bounds__(256) void conv_in_rgb_kernel(const float* x, const unsigned char* img, const float* w,
+                                                           const float* bias, bf16_t* y, int B, int H, int W, int Cout,
+                                                           int groups_per_wave) {
+    constexpr int K = 27;
+    __shared__ unsigned lut[256];                // 8-bit path: bf16 hi | lo << 16 of (float)p / 127.5f - 1.f
+    if (img) {                                   // (block-uniform)
+        const float v = (float)(int)threadIdx.x / 127.5f - 1.f;
+        const bf16_t h = f2bf(v);
+        lut[threadIdx.x] = (unsigned)h | ((unsigned)f2bf(v - bf2f(h)) << 16);
+        __syncthreads();
+    }
+    const int lane = lane_id(), wave = uniform((int)(threadIdx.x >> 6)), fr = lane & 15, fg = lane >> 4;
+    const int p0 = (int)blockIdx.y * RGB_PAIRS;
+    const int np = min(RGB_PAIRS, Cout / 32 - p0);
+    bf16x8 whi[RGB_PAIRS][2], wlo[RGB_PAIRS][2];
+    float bia[RGB_PAIRS][8];
+#pragma unroll
+    for (int q = 0; q < RGB_PAIRS; ++q) {
+        const bool live = q < np;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int n = 32 * (p0 + q) + 8 * (fr >> 2) + 4 * j + (fr & 3);       // the channel this lane's A row carries
+            u32x4 hi = {0u, 0u, 0u, 0u}, lo = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int i = 0; i < 8; i += 2) {
+                const int k = 8 * fg + i;
+                const float a = (live && k < K) ? w[(int64_t)n * K + k] : 0.f;
+                const float b = (live && k + 1 < K) ? w[(int64_t)n * K + k + 1] : 0.f;
+                const unsigned h2 = pack_bf2(a, b);
+                hi[i >> 1] = h2;
+                lo[i >> 1] = pack_bf2(a - bf2f((bf16_t)(h2 & 0xffffu)), b - bf2f((bf16_t)(h2 >> 16)));
+            }
+            whi[q][j] = __builtin_bit_cast(bf16x8, hi);
+            wlo[q][j] = __builtin_bit_cast(bf16x8, lo);
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) bia[q][e] = live ? bias[32 * (p0 + q) + 8 * fg + e] : 0.f;
+    }
+    const int npix = B * H * W;                  // (host: < 2^30; 32-bit divisions only)
+    for (int g = 0; g < groups_per_wave; ++g) {
+        const int group = ((int)blockIdx.x * 4 + wave) * groups_per_wave + g;      // wave-uniform
+        if ((int64_t)group * 16 >= npix) break;
+        const int pix = group * 16 + fr;
+        const bool pv = pix < npix;
+        const unsigned pp = pv ? (unsigned)pix : 0u;
+        const unsigned row = pp / (unsigned)W;
+        const int px = (int)(pp - row * (unsigned)W), b = (int)(row / (unsigned)H), py = (int)(row - (unsigned)b * (unsigned)H);
+        u32x4 th = {0u, 0u, 0u, 0u}, tl = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int k = 8 * fg + i;
+            const int c = k / 9, tap = k - 9 * c;
+            const int iy = py + tap / 3 - 1, ix = px + tap % 3 - 1;
+            unsigned hl = 0u;                    // hi | lo << 16
+            if (pv && k < K && iy >= 0 && iy < H && ix >= 0 && ix < W) {
+                if (img) {
+                    hl = lut[img[((int64_t)(b * H + iy) * W + ix) * 3 + c]];
+                } else {
+                    const float v = x[((int64_t)(b * 3 + c) * H + iy) * W + ix];
+                    const bf16_t h = f2bf(v);
+                    hl = (unsigned)h | ((unsigned)f2bf(v - bf2f(h)) << 16);
+                }
+            }
+            th[i >> 1] |= (hl & 0xffffu) << ((i & 1) * 16);
+            tl[i >> 1] |= (hl >> 16) << ((i & 1) * 16);
+        }
+        const bf16x8 xh = __builtin_bit_cast(bf16x8, th), xl = __builtin_bit_cast(bf16x8, tl);
+#pragma unroll
+        for (int q = 0; q < RGB_PAIRS; ++q) {
+            if (q >= np) break;
+            float o[8];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+                acc = mfma16(wlo[q][j], xh, acc);
+                acc = mfma16(whi[q][j], xl, acc);
+                acc = mfma16(whi[q][j], xh, acc);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) o[4 * j + r] = acc[r] + bia[q][4 * j + r];
+            }
+            if (pv) *(u32x4*)(y + (int64_t)pix * Cout + 32 * (p0 + q) + 8 * fg) = pack8(o);
+        }
+    }
+}
+
+// ---- VAE encoder exit: conv_out (3x3 pad 1, C -> 8) + quant_conv (8 x 8, fp32) + the diagonal-Gaussian sample ---------------
+// Same mapping as conv_out_rgb_kernel with 8 weight rows: the accumulators of pixel fr live in the lanes fg = 0 (rows 0..3) and
+// fg = 1 (rows 4..7), and meet in LDS, where one lane per pixel applies quant_conv to the 8 fp32 sums (never folded into the
+// bf16 weights) and writes, either or both: moments fp32 NCHW (batch, 8, h, w) = [mean | logvar], and latents fp32 NCHW
+// (batch, 4, h, w) = scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * noise); noise = NULL: scale * mean (the mode).
+__global__ __launch_bounds__(256) void conv_out_moments_kernel(const bf16_t* x, const bf16_t* w, const float* bias, const float* qw,
+                                                                const float* qb, const float* noise, float* moments,
+                                                                float* latents, float scale, int B, int H, int W, int C) {
+    constexpr int COUT = 8;
+    __shared__ f32x4 red[4][64];
+    const int lane = lane_id(), wave = uniform((int)(threadIdx.x >> 6)), fr = lane & 15, fg = lane >> 4;
+    const int npix = B * H * W, pix = (int)blockIdx.x * 16 + fr;       // (host: < 2^30; 32-bit divisions only)
+    const bool pv = pix < npix;
+    const unsigned pp = pv ? (unsigned)pix : 0u;
+    const unsigned row = pp / (unsigned)W;
+    const int px = (int)(pp - row * (unsigned)W), b = (int)(row / (unsigned)H), py = (int)(row - (unsigned)b * (unsigned)H);
+    const int nkc = C / 32;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    const u32x4 z = {0u, 0u, 0u, 0u};
+    constexpr int UU = 4;                                  // units (x 3 taps) in flight per wave
+    const int nunits = 3 * nkc;
+    for (int u0 = wave; u0 < nunits; u0 += 4 * UU) {
+        u32x4 xv[UU][3], wv[UU][3];
+#pragma unroll
+        for (int uu = 0; uu < UU; ++uu) {
+            const int unit = u0 + 4 * uu;
+            const int cb = unit / 3, ky = unit - 3 * cb;
+            const int iy = py + ky - 1;
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx) {
+                const int ix = px + kx - 1;
+                const bool ok = unit < nunits && pv && iy >= 0 && iy < H && ix >= 0 && ix < W;
+                xv[uu][kx] = ok ? *(const u32x4*)(x + ((int64_t)(b * H + iy) * W + ix) * C + cb * 32 + fg * 8) : z;
+                wv[uu][kx] = (unit < nunits && fr < COUT) ? *(const u32x4*)(w + (int64_t)(fr * 9 + ky * 3 + kx) * C + cb * 32 + fg * 8) : z;
+            }
+        }
+#pragma unroll
+        for (int uu = 0; uu < UU; ++uu)
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx)
+                acc = mfma16(__builtin_bit_cast(bf16x8, wv[uu][kx]), __builtin_bit_cast(bf16x8, xv[uu][kx]), acc);
+    }
+    red[wave][lane] = acc;
+    __syncthreads();
+    if (wave == 0 && fg == 0 && pv) {
+        float v[COUT], m[COUT];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {                      // rows 4 h + r of column (pixel) fr: lane 16 h + fr
+            const f32x4 a0 = red[0][16 * h + fr], a1 = red[1][16 * h + fr], a2 = red[2][16 * h + fr], a3 = red[3][16 * h + fr];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v[4 * h + r] = (a0[r] + a1[r]) + (a2[r] + a3[r]) + bias[4 * h + r];
+        }
+#pragma unroll
+        for (int o = 0; o < COUT; ++o) {
+            float s = qb[o];
+#pragma unroll
+            for (int i = 0; i < COUT; ++i) s += qw[o * COUT + i] * v[i];
+            m[o] = s;
+            if (moments) moments[((int64_t)(b * COUT + o) * H + py) * W + px] = s;
+        }
+        if (latents) {
+#pragma unroll
+            for (int ch = 0; ch < 4; ++ch) {
+                const int64_t at = ((int64_t)(b * 4 + ch) * H + py) * W + px;
+                float val = m[ch];
+                if (noise) val += expf(0.5f * fminf(fmaxf(m[4 + ch], -30.f), 20.f)) * noise[at];
+                latents[at] = scale * val;
+            }
+        }
+    }
+}
+
 // dgrad of conv_out: dx[pix][c] = sum_{tap,o} dy[b][o][pix - off(tap)] * w[o][tap][c]
 template <int COUT>
 __global__ __launch_bounds__(256) void conv_out_bwd_kernel(const float* dy, const bf16_t* w, bf16_t* dx, int B,
@@ -1009,6 +1177,32 @@ extern "C" int leco_conv_out_rgb(const void* x, const void* w, const float* bias
                        (const bf16_t*)x, (const bf16_t*)w, bias, y, (unsigned char*)img, batch, h, wd, c);
     return check_launch("leco_conv_out_rgb");
 }
+extern "C" int leco_conv_in_rgb(const float* x, const void* img, const float* w, const float* bias, void* y, int32_t batch,
+                                int32_t h, int32_t wd, int32_t cout, leco_stream_t stream) {
+    if (!x && !img) return fail(-EINVAL, "conv_in_rgb: neither x (fp32 NCHW) nor img (uint8 NHWC) given");
+    if (x && img) return fail(-EINVAL, "conv_in_rgb: both x and img given; the image comes from exactly one of them");
+    if (!w || !bias || !y) return fail(-EINVAL, "conv_in_rgb: null weight / bias / output");
+    if (cout <= 0 || cout % 32) return fail(-EINVAL, "conv_in_rgb: Cout=%d %% 32 != 0", cout);
+    const int64_t npix = (int64_t)batch * h * wd;
+    if (batch <= 0 || h <= 0 || wd <= 0 || npix >= (1ll << 30)) return fail(-EINVAL, "conv_in_rgb: batch * h * w out of range");
+    const int64_t groups = (npix + 15) / 16;
+    const int gpw = groups >= 16384 ? 4 : (groups >= 4096 ? 2 : 1);       // >= 1024 workgroups where the image has them
+    hipLaunchKernelGGL(conv_in_rgb_kernel, dim3((unsigned)((groups + 4 * gpw - 1) / (4 * gpw)), (unsigned)((cout + 127) / 128)),
+                       dim3(256), 0, LECO_STREAM, x, (const unsigned char*)img, w, bias, (bf16_t*)y, batch, h, wd, cout, gpw);
+    return check_launch("leco_conv_in_rgb");
+}
+extern "C" int leco_conv_out_moments(const void* x, const void* w, const float* bias, const float* qw, const float* qb,
+                                     const float* noise, float* moments, float* latents, float scale, int32_t batch, int32_t h,
+                                     int32_t wd, int32_t c, leco_stream_t stream) {
+    if (c <= 0 || c % 32) return fail(-EINVAL, "conv_out_moments: C=%d %% 32 != 0", c);
+    if (!moments && !latents) return fail(-EINVAL, "conv_out_moments: neither moments nor latents given");
+    if (!x || !w || !bias || !qw || !qb) return fail(-EINVAL, "conv_out_moments: null input / weight / bias / quant_conv operand");
+    const int64_t npix = (int64_t)batch * h * wd;
+    if (batch <= 0 || h <= 0 || wd <= 0 || npix >= (1ll << 30)) return fail(-EINVAL, "conv_out_moments: batch * h * w out of range");
+    hipLaunchKernelGGL(conv_out_moments_kernel, dim3((unsigned)((npix + 15) / 16)), dim3(256), 0, LECO_STREAM, (const bf16_t*)x,
+                       (const bf16_t*)w, bias, qw, qb, noise, moments, latents, scale, batch, h, wd, c);
+    return check_launch("leco_conv_out_moments");
+}
 extern "C" int leco_conv_out_bwd(const float* dy, const void* w, void* dx, int32_t batch, int32_t h, int32_t wd,
                                  int32_t c, int32_t cout, leco_stream_t stream) {
     if (cout != 4 || c % 8) return fail(-EINVAL, "conv_out_bwd: needs Cout=4, C %% 8 == 0");
@@ -1209,6 +1403,8 @@ extern "C" int leco_lora_wgrad_conv(const void* p, int64_t ldp, const void* q, i
                                     int64_t g_sc, int32_t m, int32_t r, int32_t cols, float scale, int32_t a_mode,
                                     int32_t h_out, int32_t w_out, int32_t h_in, int32_t w_in, int32_t kh, int32_t kw,
                                     float* part, int64_t part_bytes, leco_stream_t stream) {
+    if (a_mode == LECO_A_CONV3_S2_PAD01)
+        return fail(-EINVAL, "lora_wgrad_conv: LECO_A_CONV3_S2_PAD01 is a forward gather of leco_gemm only (no LoRA weight gradient)");
     if (a_mode < LECO_A_CONV3_S1 || a_mode > LECO_A_CONV3_UP2) return fail(-EINVAL, "lora_wgrad_conv: bad a_mode %d", a_mode);
     return wgrad_launch(p, ldp, q, ldq, g, g_sj, g_sc, m, r, cols, scale, WgradConv{a_mode, h_out, w_out, h_in, w_in, kh, kw},
                         part, part_bytes, LECO_STREAM);

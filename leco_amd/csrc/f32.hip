@@ -675,6 +675,8 @@ int f32_gemm_validate(const leco_gemm_args& a) {
     if ((a.lda0 | a.ldw | (a.a1 ? a.lda1 : 0) | (a.a_ext ? (a.ld_aext | a.ld_wext | a.ext_k) : 0)) % 4)
         return fail(-EINVAL, "leco_f32_gemm: operand strides must keep 16-byte alignment");
     if (a.a_ext && !a.w_ext) return fail(-EINVAL, "leco_f32_gemm: a_ext without w_ext");
+    if (a.a_mode == LECO_A_CONV3_S2_PAD01)
+        return fail(-EINVAL, "leco_f32_gemm: LECO_A_CONV3_S2_PAD01 is a bf16 forward gather (leco_gemm) only");
     if (a.a_mode < LECO_A_PLAIN || a.a_mode > LECO_A_CONV3_TR2) return fail(-EINVAL, "leco_f32_gemm: bad a_mode");
     if (a.a_mode != LECO_A_PLAIN && (int64_t)a.batch * a.h_out * a.w_out != a.m) return fail(-EINVAL, "leco_f32_gemm: conv m mismatch");
     if (a.rowbias && a.rows_per_group <= 0) return fail(-EINVAL, "leco_f32_gemm: rowbias needs rows_per_group");

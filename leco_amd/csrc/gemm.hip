@@ -128,7 +128,7 @@ __global__ __launch_bounds__(NWM * 128) void gemm_kernel(const leco_gemm_args p,
     const int k_split = a1 ? p.k_split : 0x7fffffff;
 
     // Per-lane addressing state, built once.  Every staged A row of this lane (GA of them) keeps
-    //   plain: its row index;  conv: qy = oy*sy - 1, qx = ox*sy - 1 (tap (kh,kw) reads u = q + k, source
+    //   plain: its row index;  conv: qy = oy*sy - 1, qx = ox*sy - 1 (offset 0 for LECO_A_CONV3_S2_PAD01) (tap (kh,kw) reads u = q + k, source
     //   pixel u >> dv), the sample's first pixel row b*h_in, and a 6-bit validity mask over the 3 vertical /
     //   3 horizontal taps (padding, stride-2 parity of the transposed gather, m < M) -- so the per-K-step
     //   address is a few adds / shifts, two 24-bit multiply-adds and one select against the zero page: no
@@ -151,11 +151,12 @@ __global__ __launch_bounds__(NWM * 128) void gemm_kernel(const leco_gemm_args p,
             const int pb = (int)arow[i] / hw;
             const int rem = (int)arow[i] - pb * hw;
             const int py = rem / p.w_out, px = rem - py * p.w_out;
-            const int sy = (p.a_mode == LECO_A_CONV3_S2) ? 2 : 1;
+            const int sy = (p.a_mode == LECO_A_CONV3_S2 || p.a_mode == LECO_A_CONV3_S2_PAD01) ? 2 : 1;
+            const int pad = (p.a_mode == LECO_A_CONV3_S2_PAD01) ? 0 : 1;      // PAD01: no top / left padding
             const int odd_mask = (p.a_mode == LECO_A_CONV3_TR2) ? 1 : 0;
             const int lim_y = p.h_in << dv, lim_x = p.w_in << dv;
-            qy[i] = py * sy - 1;
-            qx[i] = px * sy - 1;
+            qy[i] = py * sy - pad;
+            qx[i] = px * sy - pad;
             pbh[i] = pb * p.h_in;
             unsigned vm = 0;
 #pragma unroll
@@ -847,13 +848,17 @@ int validate(const leco_gemm_args& a) {
     if (a.act == LECO_ACT_GEGLU && (a.n % 128 || !a.c || a.residual || a.rowbias || a.c_f32 || a.ldc % 8))
         return fail(-EINVAL, "leco_gemm: LECO_ACT_GEGLU needs n %% 128 == 0, a bf16 output and no residual / rowbias / fp32 copy");
     if (a.act < LECO_ACT_NONE || a.act > LECO_ACT_GELU) return fail(-EINVAL, "leco_gemm: bad act %d", a.act);
-    if (a.a_mode < LECO_A_PLAIN || a.a_mode > LECO_A_CONV3_TR2) return fail(-EINVAL, "leco_gemm: bad a_mode %d", a.a_mode);
+    if (a.a_mode < LECO_A_PLAIN || a.a_mode > LECO_A_CONV3_S2_PAD01) return fail(-EINVAL, "leco_gemm: bad a_mode %d", a.a_mode);
     if ((a.lda0 | a.ldw | (a.a1 ? a.lda1 : 0) | (a.a_ext ? (a.ld_aext | a.ld_wext) : 0)) % 8)
         return fail(-EINVAL, "leco_gemm: operand strides must be multiples of 8 elements (16-byte DMA)");
     if (a.a_mode != LECO_A_PLAIN) {
         if (a.k % 9 || (a.k / 9) % BK) return fail(-EINVAL, "leco_gemm: conv needs k = 9*Cin, Cin %% 64 == 0 (k=%d)", a.k);
         if ((int64_t)a.batch * a.h_out * a.w_out != a.m) return fail(-EINVAL, "leco_gemm: conv m != batch*h_out*w_out");
         if (a.a1 && (a.k_split % BK)) return fail(-EINVAL, "leco_gemm: conv k_split %% 64 != 0");
+        if (a.a_mode == LECO_A_CONV3_S2_PAD01 && ((a.h_in | a.w_in) % 2 || a.h_in <= 0 || a.w_in <= 0 || a.h_out * 2 != a.h_in ||
+                                                   a.w_out * 2 != a.w_in))
+            return fail(-EINVAL, "leco_gemm: LECO_A_CONV3_S2_PAD01 needs even h_in, w_in and h_out = h_in / 2, w_out = w_in / 2 "
+                                 "(in %dx%d, out %dx%d)", a.h_in, a.w_in, a.h_out, a.w_out);
     } else if (a.a1 && (a.k_split % BK)) {
         return fail(-EINVAL, "leco_gemm: k_split %% 64 != 0");
     }
@@ -970,6 +975,8 @@ extern "C" int leco_gemm_ex(const leco_gemm_args* args, int tile, int split_k, v
         }
     }
     if (tile >= 7 && tile <= 10) {
+        if (args->a_mode == LECO_A_CONV3_S2_PAD01)
+            return fail(-EINVAL, "leco_gemm: tile %d is the patch-staged stride-1 convolution; it does not take LECO_A_CONV3_S2_PAD01", tile);
         rc = conv_patch_try(*args, tile, split_k, (float*)workspace, s, tl_describe, tl_describe_len);
         if (rc == 1) return leco_gemm_ex(args, -1, 0, workspace, workspace_bytes, stream);
         if (rc < 0 || tl_describe) return rc;

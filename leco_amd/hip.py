@@ -16,7 +16,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libleco_hip.so")
 
-A_PLAIN, A_CONV3_S1, A_CONV3_S2, A_CONV3_UP2, A_CONV3_TR2 = range(5)
+A_PLAIN, A_CONV3_S1, A_CONV3_S2, A_CONV3_UP2, A_CONV3_TR2, A_CONV3_S2_PAD01 = range(6)
 ACT_NONE, ACT_SILU, ACT_GEGLU, ACT_QUICK_GELU, ACT_GELU = 0, 1, 2, 3, 4
 
 

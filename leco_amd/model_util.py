@@ -296,9 +296,9 @@ def load_synthetic_model(kind: str, seed: int = 1234):
 def _load_state_into_vae(vae, sd, what: str):
     missing, unexpected = vae.load_state_dict(sd, strict=False)
     if missing:
-        raise KeyError(f"{what}: the VAE decoder lacks {missing[0]!r}" + (f" (and {len(missing) - 1} more)" if len(missing) > 1 else ""))
+        raise KeyError(f"{what}: the VAE lacks {missing[0]!r}" + (f" (and {len(missing) - 1} more)" if len(missing) > 1 else ""))
     if unexpected:
-        raise KeyError(f"{what}: unexpected VAE decoder key {unexpected[0]!r}"
+        raise KeyError(f"{what}: unexpected VAE key {unexpected[0]!r}"
                        + (f" (and {len(unexpected) - 1} more)" if len(unexpected) > 1 else ""))
     return vae
 
@@ -306,15 +306,17 @@ def _load_state_into_vae(vae, sd, what: str):
 SYNTHETIC_VAE = {"sd15": 0.18215, "sd21": 0.18215, "sdxl": 0.13025}      # real decoder shape, scaling factor
 
 
-def load_vae(path: str, precision: str = "bfloat16", scaling_factor: Optional[float] = None):
-    """The VAE decoder (`leco_amd.vae.AutoencoderKL`) of
+def load_vae(path: str, precision: str = "bfloat16", scaling_factor: Optional[float] = None, encoder: bool = False):
+    """The VAE (`leco_amd.vae.AutoencoderKL`: the decoder half; with ``encoder=True`` also ``encoder`` + ``quant_conv``, for
+    `encode` / `encode_to_latents`) of
 
     * a diffusers pipeline folder (its ``vae/`` subfolder) or the ``vae`` folder itself: ``config.json`` +
       ``diffusion_pytorch_model.safetensors`` / ``.bin``; both attention spellings (``to_q`` ... / ``query`` ...);
-    * a single-file LDM checkpoint (``first_stage_model.*``; encoder and ``quant_conv`` are ignored);
+    * a single-file LDM checkpoint (``first_stage_model.*``; without ``encoder=True`` its encoder and ``quant_conv`` are ignored);
     * ``synthetic:<sd15|sd21|sdxl>`` (the real decoder shape, seeded random weights) / ``synthetic:<tiny|tiny_xl>``.
 
-    A missing or unexpected decoder key is an error naming it.  The decoder computes in bfloat16 only."""
+    A missing or unexpected key of a half that is built is an error naming it.  The VAE computes in bfloat16 only.  Synthetic
+    encoder weights come from a generator of their own: the decoder weights do not depend on ``encoder``."""
     from . import ckpt_convert as cc
     from . import vae as V
     if precision not in ("bfloat16", "bf16", torch.bfloat16):
@@ -328,7 +330,7 @@ def load_vae(path: str, precision: str = "bfloat16", scaling_factor: Optional[fl
             cfg = V.tiny_vae_config(0.18215 if kind == "tiny" else 0.13025)
         else:
             raise ValueError(f"{p}: unknown synthetic VAE (sd15 | sd21 | sdxl | tiny | tiny_xl)")
-        return V.init_synthetic_vae_(V.AutoencoderKL(cfg))
+        return V.init_synthetic_vae_(V.AutoencoderKL(cfg, encoder=encoder))
     if os.path.isdir(p):
         d = os.path.join(p, "vae") if os.path.isfile(os.path.join(p, "vae", "config.json")) else p
         if not os.path.isfile(os.path.join(d, "config.json")):
@@ -342,10 +344,10 @@ def load_vae(path: str, precision: str = "bfloat16", scaling_factor: Optional[fl
             sd = load_file(st)
         else:
             sd = torch.load(os.path.join(d, "diffusion_pytorch_model.bin"), map_location="cpu")
-        return _load_state_into_vae(V.AutoencoderKL(cfg), cc.normalise_vae_keys(sd), d)
+        return _load_state_into_vae(V.AutoencoderKL(cfg, encoder=encoder), cc.normalise_vae_keys(sd, encoder), d)
     if p.endswith(".ckpt") or p.endswith(".safetensors"):
-        sd = cc.convert_ldm_vae(cc.read_checkpoint(p))
-        return _load_state_into_vae(V.AutoencoderKL(cc.detect_vae_config(sd, scaling_factor)), sd, p)
+        sd = cc.convert_ldm_vae(cc.read_checkpoint(p), encoder)
+        return _load_state_into_vae(V.AutoencoderKL(cc.detect_vae_config(sd, scaling_factor), encoder=encoder), sd, p)
     raise FileNotFoundError(f"{p}: not a local diffusers folder, single-file checkpoint or synthetic:<sd15|sd21|sdxl|tiny|tiny_xl>")
 
 

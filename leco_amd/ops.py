@@ -41,6 +41,8 @@ _SIGS = {
     "leco_conv_out_bwd": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
     "leco_latent_affine": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp],
     "leco_conv_out_rgb": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
+    "leco_conv_in_rgb": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
+    "leco_conv_out_moments": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _i32, _i32, _i32, _i32, _vp],
     "leco_timestep_embedding": [_vp, _vp, _i32, _i32, _i32, _vp, _vp],
     "leco_advance": [_vp, _vp],
     "leco_cfg_ddim_step": [_vp, _vp, _vp, _vp, _vp, _f32, _i64, _vp],
@@ -300,6 +302,19 @@ def latent_affine(x, w, bias, y, batch, hw, cin, cout, in_scale) -> Op:
 def conv_out_rgb(x, w, bias, y, img, batch, h, wd, c) -> Op:
     """3x3 conv to RGB: ``y`` fp32 NCHW and / or ``img`` uint8 NHWC (either may be None), see include/leco_hip.h."""
     return Op("leco_conv_out_rgb", (ptr(x), ptr(w), ptr(bias), ptr(y), ptr(img), batch, h, wd, c), keep=(x, w, bias, y, img))
+
+
+def conv_in_rgb(x, img, w, bias, y, batch, h, wd, cout) -> Op:
+    """The VAE encoder's conv_in: ``x`` fp32 NCHW in [-1, 1] or ``img`` uint8 NHWC (exactly one, the other None) -> channels-last
+    bf16 ``y``; ``w`` fp32 [cout][3][3][3], see include/leco_hip.h."""
+    return Op("leco_conv_in_rgb", (ptr(x), ptr(img), ptr(w), ptr(bias), ptr(y), batch, h, wd, cout), keep=(x, img, w, bias, y))
+
+
+def conv_out_moments(x, w, bias, qw, qb, noise, moments, latents, scale, batch, h, wd, c) -> Op:
+    """The VAE encoder's exit: 3x3 conv to 8 channels + quant_conv (fp32 8x8) -> ``moments`` fp32 (B,8,h,w) and / or
+    ``latents`` fp32 (B,4,h,w) = scale * (mean + std * noise) (``noise`` None: the mode), see include/leco_hip.h."""
+    return Op("leco_conv_out_moments", (ptr(x), ptr(w), ptr(bias), ptr(qw), ptr(qb), ptr(noise), ptr(moments), ptr(latents),
+                                        float(scale), batch, h, wd, c), keep=(x, w, bias, qw, qb, noise, moments, latents))
 
 
 def conv_out_bwd(dy, w, dx, batch, h, wd, c, cout) -> Op:

@@ -19,6 +19,14 @@ class SchedulerOutput:
         self.pred_original_sample = pred_original_sample
 
 
+def _alpha_add_noise(alphas_cumprod, original_samples, noise, timesteps):
+    """diffusers' add_noise of the alpha-based schedulers: sqrt(abar_t) x + sqrt(1 - abar_t) n, t a scalar or one per sample."""
+    t = torch.as_tensor(timesteps).reshape(-1).long().cpu()
+    a = alphas_cumprod[t].to(device=original_samples.device, dtype=original_samples.dtype)
+    a = a.reshape(-1, *([1] * (original_samples.ndim - 1)))
+    return a.sqrt() * original_samples + (1 - a).sqrt() * noise
+
+
 class DDIMScheduler:
     order = 1
 
@@ -72,6 +80,9 @@ class DDIMScheduler:
             raise ValueError("call set_timesteps first")
         cx, ce = self._coef(int(timestep))
         return SchedulerOutput(cx * sample + ce * model_output)
+
+    def add_noise(self, original_samples, noise, timesteps):
+        return _alpha_add_noise(self.alphas_cumprod, original_samples, noise, timesteps)
 
 
 # =============================================================================================
@@ -138,6 +149,13 @@ class _SigmaBase:
         """derivative (x - pred_x0) / sigma = d_x x + d_e out."""
         px, pe = self._x0_coef(sigma)
         return (1.0 - px) / sigma, -pe / sigma
+
+    def add_noise(self, original_samples, noise, timesteps):
+        """diffusers' add_noise of the sigma-space schedulers: x + sigma_t n, sigma_t looked up in the CURRENT schedule."""
+        t = torch.as_tensor(timesteps).reshape(-1)
+        sig = torch.tensor([float(self.sigmas[self._index(v)]) for v in t], device=original_samples.device,
+                           dtype=original_samples.dtype).reshape(-1, *([1] * (original_samples.ndim - 1)))
+        return original_samples + sig * noise
 
     def _scale_next(self, i: int) -> float:
         s = float(self.sigmas[i + 1]) if i + 1 < len(self.sigmas) - 1 else 0.0
@@ -283,6 +301,9 @@ class DDPMScheduler:
         if noise is None:
             noise = torch.randn(model_output.shape, generator=generator, device=model_output.device, dtype=model_output.dtype)
         return SchedulerOutput(cx * sample + ce * model_output + cn * noise)
+
+    def add_noise(self, original_samples, noise, timesteps):
+        return _alpha_add_noise(self.alphas_cumprod, original_samples, noise, timesteps)
 
 
 def create_noise_scheduler(scheduler_name: str = "ddpm", prediction_type: str = "epsilon"):

@@ -20,7 +20,7 @@ from leco_amd import model_util, prompt_util, train_util  # noqa: E402
 from leco_amd.lora import LoRANetwork  # noqa: E402
 from leco_amd.train import FusedStep  # noqa: E402
 
-AMODE = {0: "plain", 1: "conv3", 2: "conv3s2", 3: "conv3up2", 4: "conv3tr2"}
+AMODE = {0: "plain", 1: "conv3", 2: "conv3s2", 3: "conv3up2", 4: "conv3tr2", 5: "conv3s2pad01"}
 
 
 def describe(op):

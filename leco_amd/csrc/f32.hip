@@ -675,6 +675,9 @@ int f32_gemm_validate(const leco_gemm_args& a) {
     if ((a.lda0 | a.ldw | (a.a1 ? a.lda1 : 0) | (a.a_ext ? (a.ld_aext | a.ld_wext | a.ext_k) : 0)) % 4)
         return fail(-EINVAL, "leco_f32_gemm: operand strides must keep 16-byte alignment");
     if (a.a_ext && !a.w_ext) return fail(-EINVAL, "leco_f32_gemm: a_ext without w_ext");
+    // the last K chunk of a k % 16 != 0 problem continues into the extension columns: both operands must be there
+    if (a.ext_k < 0 || (a.ext_k > 0 && (!a.a_ext || !a.w_ext)))
+        return fail(-EINVAL, "leco_f32_gemm: ext_k = %d needs a_ext and w_ext", a.ext_k);
     if (a.a_mode == LECO_A_CONV3_S2_PAD01)
         return fail(-EINVAL, "leco_f32_gemm: LECO_A_CONV3_S2_PAD01 is a bf16 forward gather (leco_gemm) only");
     if (a.a_mode < LECO_A_PLAIN || a.a_mode > LECO_A_CONV3_TR2) return fail(-EINVAL, "leco_f32_gemm: bad a_mode");
@@ -685,8 +688,10 @@ int f32_gemm_validate(const leco_gemm_args& a) {
 size_t attn_lds_fwd(int d) { return (size_t)(AQ * d + AK * (d + 1) + AK * d + AQ * (AK + 1)) * 4; }
 size_t attn_lds_bwd(int d) { return (size_t)(2 * AQ * d + 2 * AK * (d + 1) + 2 * AQ * (AK + 1) + 2 * AK) * 4; }
 template <typename K>
-void set_lds(K kernel, size_t bytes) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+int set_lds(K kernel, size_t bytes, const char* what) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) return fail(-EIO, "%s: %zu bytes of dynamic LDS refused: %s", what, bytes, hipGetErrorString(e));
+    return 0;
 }
 }  // namespace
 }  // namespace leco
@@ -704,7 +709,7 @@ extern "C" int leco_f32_attention_fwd(const void* q, int64_t ldq, int64_t bsq, c
                                       int64_t ldv, int64_t bsv, void* o, int64_t ldo, int64_t bso, float* lse, int32_t batch,
                                       int32_t heads, int32_t sq, int32_t skv, int32_t d, float scale, leco_stream_t stream) {
     if (d % 4 || d > AD_MAX || d <= 0) return fail(-EINVAL, "leco_f32_attention: head_dim %d unsupported (multiple of 4, <= 160)", d);
-    set_lds(attn_fwd_f32_kernel, attn_lds_fwd(d));
+    if (const int rc = set_lds(attn_fwd_f32_kernel, attn_lds_fwd(d), "leco_f32_attention_fwd")) return rc;
     hipLaunchKernelGGL(attn_fwd_f32_kernel, dim3(cdiv(sq, AQ), heads, batch), dim3(256), attn_lds_fwd(d), LECO_STREAM, (const float*)q,
                        ldq, bsq, (const float*)k, ldk, bsk, (const float*)v, ldv, bsv, (float*)o, ldo, bso, lse, heads, sq, skv, d, scale);
     return check_launch("leco_f32_attention_fwd");
@@ -715,10 +720,10 @@ extern "C" int leco_f32_attention_bwd(const void* q, int64_t ldq, int64_t bsq, c
                                       int64_t lddk, int64_t bsdk, void* dv, int64_t lddv, int64_t bsdv, int32_t batch, int32_t heads,
                                       int32_t sq, int32_t skv, int32_t d, float scale, leco_stream_t stream) {
     if (d % 4 || d > AD_MAX || d <= 0) return fail(-EINVAL, "leco_f32_attention: head_dim %d unsupported", d);
+    if (const int rc = set_lds(attn_bwd_f32_kernel<true>, attn_lds_bwd(d), "leco_f32_attention_bwd")) return rc;
+    if (const int rc = set_lds(attn_bwd_f32_kernel<false>, attn_lds_bwd(d), "leco_f32_attention_bwd")) return rc;
     hipLaunchKernelGGL(attn_delta_f32_kernel, dim3(grid1((int64_t)batch * heads * sq)), dim3(256), 0, LECO_STREAM, (const float*)o, ldo,
                        bso, (const float*)d_o, lddo, bsdo, delta, batch, heads, sq, d);
-    set_lds(attn_bwd_f32_kernel<true>, attn_lds_bwd(d));
-    set_lds(attn_bwd_f32_kernel<false>, attn_lds_bwd(d));
     hipLaunchKernelGGL(attn_bwd_f32_kernel<true>, dim3(cdiv(sq, AQ), heads, batch), dim3(256), attn_lds_bwd(d), LECO_STREAM,
                        (const float*)q, ldq, bsq, (const float*)k, ldk, bsk, (const float*)v, ldv, bsv, (const float*)d_o, lddo, bsdo,
                        lse, (const float*)delta, (float*)dq, lddq, bsdq, (float*)nullptr, (int64_t)0, (int64_t)0, heads, sq, skv, d, scale);
@@ -742,6 +747,7 @@ extern "C" int leco_f32_groupnorm_bwd(const void* x0, int64_t ld0, const void* x
                                       int32_t groups, float eps, int32_t act, float* bstats, void* dx, int64_t lddx,
                                       leco_stream_t stream) {
     (void)eps; (void)bstats;
+    if (groups <= 0 || c % groups) return fail(-EINVAL, "leco_f32_groupnorm: c=%d groups=%d", c, groups);
     GnSrcF s{(const float*)x0, (const float*)x1, ld0, ld1, x1 ? c0 : c};
     hipLaunchKernelGGL(gn_bwd_f32_kernel, dim3(groups, batch), dim3(256), 0, LECO_STREAM, s, (const float*)dy, lddy, gamma, beta, stats,
                        hw, c, groups, act, (float*)dx, lddx);
@@ -846,6 +852,9 @@ extern "C" int leco_f32_lora_wgrad_conv(const void* p, int64_t ldp, const void* 
                                         int32_t h_in, int32_t w_in, int32_t kh, int32_t kw, float* part, int64_t part_bytes,
                                         leco_stream_t stream) {
     (void)part; (void)part_bytes;
+    // as leco_lora_wgrad_conv: the transposed and the bottom / right padded gathers have no LoRA weight gradient
+    if (a_mode < LECO_A_PLAIN || a_mode > LECO_A_CONV3_UP2)
+        return fail(-EINVAL, "leco_f32_lora_wgrad_conv: a_mode %d unsupported (PLAIN / CONV3_S1 / CONV3_S2 / CONV3_UP2)", a_mode);
     hipLaunchKernelGGL(lora_wgrad_f32_kernel, dim3(grid1((int64_t)r * cols)), dim3(256), 0, LECO_STREAM, (const float*)p, ldp,
                        (const float*)q, ldq, g, g_sj, g_sc, m, r, cols, scale, a_mode, h_out, w_out, h_in, w_in, kh, kw);
     return check_launch("leco_f32_lora_wgrad_conv");

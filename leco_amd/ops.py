@@ -418,6 +418,18 @@ def lora_wgrad(p, ldp, q, ldq, g, g_sj, g_sc, m, r, cols, scale, part: Optional[
                                   0 if part is None else part.numel() * part.element_size()), keep=(part,))
 
 
+def lora_wgrad_conv(p, ldp, q, ldq, g, g_sj, g_sc, m, r, cols, scale, a_mode, h_out, w_out, h_in, w_in, kh, kw,
+                    part: Optional[torch.Tensor] = None) -> Op:
+    """`lora_wgrad` with q gathered like tap (kh, kw) of a 3x3 convolution (a_mode A_CONV3_S1 / S2 / UP2)."""
+    return Op("leco_lora_wgrad_conv", (p, ldp, q, ldq, g, g_sj, g_sc, m, r, cols, scale, a_mode, h_out, w_out, h_in, w_in, kh, kw,
+                                       ptr(part), 0 if part is None else part.numel() * part.element_size()), keep=(part,))
+
+
+def rowgroup_sum(x, ldx, out, ldo, groups, rows_per_group, cols) -> Op:
+    """out[g][c] = sum of x[g * rows_per_group + r][c] over r (fp32 ``out``)."""
+    return Op("leco_rowgroup_sum", (ptr(x), ldx, ptr(out), ldo, groups, rows_per_group, cols), keep=(x, out))
+
+
 def lora_wgrad_grouped(problems: list, device) -> Optional[Op]:
     """ONE launch for a list of weight-gradient problems.  Each entry: dict(p, ldp, q, ldq, g, g_sj, g_sc, m, r, cols,
     scale[, a_mode, h_out, w_out, h_in, w_in, kh, kw]) with raw device addresses, as for `lora_wgrad` /

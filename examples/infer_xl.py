@@ -18,11 +18,15 @@ can see what a trained LoRA does to a given picture.
 
     python examples/infer_xl.py --model synthetic:tiny_xl --height 128 --width 128 --steps 4 --image out.png
     python examples/infer_xl.py --model synthetic:tiny_xl --height 128 --width 128 --steps 4 --init_image out.png --strength 0.5 --image out2.png
+    python examples/infer_xl.py --model synthetic:tiny_xl --height 128 --width 128 --steps 4 --lora x_last.safetensors --lora_scales -2,-1,0,1,2 --image sheet.png
     python examples/infer_xl.py --model /models/sdxl-base --lora output/x_last.safetensors --prompt "a photo of lemonade" --image lemonade.png
+
+`--lora FILE` reads rank, alpha and coverage from the file (`--rank` / `--alpha` override).  `--lora_scales` is the slider
+sweep: one seed and one initial latent (or `--init_image`) at every strength, all strengths through each denoising step as one
+batch (`LoRANetwork.set_strengths`, bf16 only); `--image` becomes a contact sheet, left to right, `--out` holds [n,4,h,w].
 """
 import argparse
 import contextlib
-import io
 import os
 import sys
 
@@ -32,7 +36,7 @@ from safetensors.torch import save_file
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path[:0] = [os.path.dirname(HERE), HERE]
 from leco_amd import model_util, train_util  # noqa: E402
-from leco_amd.lora import LoRANetwork  # noqa: E402
+import _lora_sweep  # noqa: E402
 from _img2img import init_latents  # noqa: E402
 
 SDXL_NOISE_OFFSET = 0.0357      # test/infer_xl.py:27
@@ -48,9 +52,7 @@ def main(argv=None):
     ap.add_argument("--width", type=int, default=768)
     ap.add_argument("--steps", type=int, default=16)
     ap.add_argument("--guidance_scale", type=float, default=7.0)
-    ap.add_argument("--lora", default=None, help="LoRA weights saved by train_lora_xl.py")
-    ap.add_argument("--rank", type=int, default=4)
-    ap.add_argument("--alpha", type=float, default=1.0)
+    _lora_sweep.add_arguments(ap)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--no_graphs", action="store_true", help="eager launches instead of one hipGraph per UNet pass")
@@ -61,7 +63,9 @@ def main(argv=None):
     ap.add_argument("--strength", type=float, default=0.6, help="img2img: 0 < S <= 1, the share of the schedule that is run")
     ap.add_argument("--native_text_encoder", action="store_true",
                     help="encode the prompts with the native CLIP text encoder (leco_amd.clip, bf16 only) instead of transformers")
-    args = ap.parse_args(argv)
+    args = ap.parse_args(_lora_sweep.join_scales(argv))
+    scales = _lora_sweep.parse_scales(ap, args)
+    n = 1 if scales is None else len(scales)
     dev = torch.device(args.device)
     dtype = torch.bfloat16
     if args.init_image and not 0.0 < args.strength <= 1.0:
@@ -76,17 +80,13 @@ def main(argv=None):
     unet.requires_grad_(False)
     unet.eval()
     unet.use_graphs = dev.type == "cuda" and not args.no_graphs
-    network = None
-    if args.lora:
-        with contextlib.redirect_stdout(io.StringIO()):
-            network = LoRANetwork(unet, rank=args.rank, multiplier=1.0, alpha=args.alpha).to(dev)
-        network.load_weights(args.lora)
+    network = _lora_sweep.load_network(unet, args, scales)
     add_time_ids = train_util.get_add_time_ids(args.height, args.width, dynamic_crops=False).to(dev)
     pos, pos_pooled = train_util.encode_prompts_xl(tokenizers, text_encoders, [args.prompt], num_images_per_prompt=1)
     neg, neg_pooled = train_util.encode_prompts_xl(tokenizers, text_encoders, [args.negative_prompt], num_images_per_prompt=1)
-    text_embeds = train_util.concat_embeddings(neg, pos, 1)
-    add_text_embeds = train_util.concat_embeddings(neg_pooled, pos_pooled, 1)
-    add_time_ids = train_util.concat_embeddings(add_time_ids, add_time_ids, 1)
+    text_embeds = train_util.concat_embeddings(neg, pos, n)
+    add_text_embeds = train_util.concat_embeddings(neg_pooled, pos_pooled, n)
+    add_time_ids = train_util.concat_embeddings(add_time_ids, add_time_ids, n)
     sched.set_timesteps(args.steps, device=dev)
     torch.manual_seed(args.seed)
     t_start = 0
@@ -96,6 +96,8 @@ def main(argv=None):
     else:
         latents = train_util.get_initial_latents(sched, 1, args.height, args.width, 1)
         latents = train_util.apply_noise_offset(latents * sched.init_noise_sigma, SDXL_NOISE_OFFSET).to(dev, dtype=dtype)
+    if scales is not None:      # one seed, one initial latent: the same start at every strength
+        latents = latents.repeat(n, 1, 1, 1)
     with (network if network is not None else contextlib.nullcontext()):
         latents = train_util.diffusion_xl(unet, sched, latents, text_embeddings=text_embeds,
                                           add_text_embeddings=add_text_embeds, add_time_ids=add_time_ids,
@@ -104,7 +106,8 @@ def main(argv=None):
               {"prompt": args.prompt, "steps": str(args.steps), "guidance_scale": str(args.guidance_scale)})
     print(f"Done. latents {tuple(latents.shape)} -> {args.out}")
     if args.image:
-        write_image(latents, args.vae or args.model, args.image, dev, use_graphs=unet.use_graphs)
+        (write_image if scales is None else _lora_sweep.write_sheet)(latents, args.vae or args.model, args.image, dev,
+                                                                      use_graphs=unet.use_graphs)
     return latents
 
 

@@ -139,6 +139,14 @@ typedef struct leco_lora_site {
 } leco_lora_site;
 
 int leco_lora_pack(const leco_lora_site* sites, int32_t nsites, leco_stream_t stream);
+/* Per-sample LoRA strength (the forward-only "sweep" plans): the low-rank image T = x down^T of a site, bf16
+ * [rows][cols] with row stride ld (elements), is scaled in place,
+ *     T[m][c] = bf16(float(T[m][c]) * strengths[m / rows_per_sample]),
+ * strengths = fp32 [rows / rows_per_sample] in DEVICE memory, read when the kernel runs (a captured graph picks up new
+ * values at replay).  cols and ld are multiples of 8 (the sites' Rp: 32 or a multiple of 64), T is 16-byte aligned,
+ * rows is a multiple of rows_per_sample; columns cols..ld are not touched. */
+int leco_lora_rowscale(void* t, int64_t ld, int32_t rows, int32_t cols, int32_t rows_per_sample, const float* strengths,
+                       leco_stream_t stream);
 
 
 /* G[j*g_sj + c*g_sc] += scale * sum_m P[m][p_off+j] * Q[m][q_off+c], j<r, c<cols (LoRA weight

@@ -96,6 +96,26 @@ __global__ __launch_bounds__(256) void add_kernel(const bf16_t* a, int64_t lda, 
     }
 }
 
+// ---- per-sample LoRA strength: T[m][c] *= strengths[m / rows_per_sample], in place, row-strided bf16 ---------
+// One 16-byte vector (8 columns) per work item; the strength is read from device memory at every launch, so a captured
+// graph sees whatever the vector holds at replay.  One fp32 multiply and one round-to-nearest-even per element.
+__global__ __launch_bounds__(256) void lora_rowscale_kernel(bf16_t* T, int64_t ld, int M, int C, int rows_per_sample,
+                                                             const float* strengths) {
+    const int nv = C / 8;
+    const int64_t total = (int64_t)M * nv;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+        const int r = (int)(e / nv);
+        const int col = (int)(e - (int64_t)r * nv) * 8;
+        const float s = strengths[r / rows_per_sample];
+        u32x4* p = (u32x4*)(T + (int64_t)r * ld + col);
+        float x[8];
+        unpack8(*p, x);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) x[i] *= s;
+        *p = pack8(x);
+    }
+}
+
 // ---- dgrad of nearest-2x upsample: dx[b][y][x][c] = sum of the 2x2 block of dy --------------------
 __global__ __launch_bounds__(256) void upsample_bwd_kernel(const bf16_t* dy, bf16_t* dx, int B, int H, int W,
                                                             int C) {
@@ -1125,6 +1145,17 @@ extern "C" int leco_add(const void* a, int64_t lda, const void* b, int64_t ldb, 
     hipLaunchKernelGGL(add_kernel, dim3(grid_for((int64_t)m * cols / 8)), dim3(256), 0, LECO_STREAM,
                        (const bf16_t*)a, lda, (const bf16_t*)b, ldb, (const bf16_t*)c, ldc, (bf16_t*)out, ldo, m, cols);
     return check_launch("leco_add");
+}
+extern "C" int leco_lora_rowscale(void* t, int64_t ld, int32_t rows, int32_t cols, int32_t rows_per_sample,
+                                  const float* strengths, leco_stream_t stream) {
+    if (!t || !strengths || rows <= 0 || cols <= 0 || rows_per_sample <= 0 || rows % rows_per_sample)
+        return fail(-EINVAL, "lora_rowscale: rows=%d must be a positive multiple of rows_per_sample=%d", rows, rows_per_sample);
+    if (cols % 8 || ld % 8 || ld < cols || ((uintptr_t)t & 15))
+        return fail(-EINVAL, "lora_rowscale: cols=%d, ld=%lld must be multiples of 8 (ld >= cols) and T 16-byte aligned", cols,
+                    (long long)ld);
+    hipLaunchKernelGGL(lora_rowscale_kernel, dim3(grid_for((int64_t)rows * cols / 8)), dim3(256), 0, LECO_STREAM, (bf16_t*)t, ld,
+                       rows, cols, rows_per_sample, strengths);
+    return check_launch("leco_lora_rowscale");
 }
 extern "C" int leco_upsample2x_bwd(const void* dy, void* dx, int32_t batch, int32_t h, int32_t w, int32_t c,
                                    leco_stream_t stream) {

@@ -68,7 +68,45 @@ class LoRAModule(nn.Module):
         self.down_off = self.up_off = -1  # element offsets into the network slab
 
 
+def _discover(prefix, root_module, target_replace_modules, train_method):
+    """Module discovery of the reference (lora.py:158-199, including its name-filter semantics): yields
+    (leaf qualified name, lora name, leaf module) in network order."""
+    for name, module in root_module.named_modules():
+        if train_method == "noxattn":
+            if "attn2" in name or "time_embed" in name:
+                continue
+        elif train_method == "innoxattn":
+            if "attn2" in name:
+                continue
+        elif train_method == "selfattn":
+            if "attn1" not in name:
+                continue
+        elif train_method == "xattn":
+            if "attn2" not in name:
+                continue
+        elif train_method == "full":
+            pass
+        else:
+            raise NotImplementedError(f"train_method: {train_method} is not implemented.")
+        if module.__class__.__name__ in target_replace_modules:
+            for child_name, child_module in module.named_modules():
+                if child_module.__class__.__name__ in ["Linear", "Conv2d"]:
+                    leaf = name + "." + child_name
+                    yield leaf, (prefix + "." + leaf).replace(".", "_"), child_module
+
+
+def _read_lora_file(file) -> dict:
+    if os.path.splitext(str(file))[1] == ".safetensors":
+        from safetensors.torch import load_file
+        return load_file(str(file))
+    return torch.load(file, map_location="cpu", weights_only=True)
+
+
 class LoRANetwork(nn.Module):
+    # per-sample strengths of the sampling path (`set_strengths`); None = the single `multiplier`
+    strengths = None
+    _strengths_version = 0
+
     def __init__(self, unet, rank: int = 4, multiplier: float = 1.0, alpha: float = 1.0,
                  train_method: TRAINING_METHODS = "full", target_replace_modules: Optional[List[str]] = None,
                  strict_reference: bool = False, strict_dtype: torch.dtype = torch.bfloat16) -> None:
@@ -99,31 +137,8 @@ class LoRANetwork(nn.Module):
 
     # ---- discovery (lora.py:158-199, including its name-filter semantics) ---------------------------
     def create_modules(self, prefix, root_module, target_replace_modules, rank, multiplier, train_method) -> list:
-        loras = []
-        for name, module in root_module.named_modules():
-            if train_method == "noxattn":
-                if "attn2" in name or "time_embed" in name:
-                    continue
-            elif train_method == "innoxattn":
-                if "attn2" in name:
-                    continue
-            elif train_method == "selfattn":
-                if "attn1" not in name:
-                    continue
-            elif train_method == "xattn":
-                if "attn2" not in name:
-                    continue
-            elif train_method == "full":
-                pass
-            else:
-                raise NotImplementedError(f"train_method: {train_method} is not implemented.")
-            if module.__class__.__name__ in target_replace_modules:
-                for child_name, child_module in module.named_modules():
-                    if child_module.__class__.__name__ in ["Linear", "Conv2d"]:
-                        leaf = name + "." + child_name
-                        lora_name = (prefix + "." + leaf).replace(".", "_")
-                        loras.append(LoRAModule(lora_name, leaf, child_module, multiplier, rank, self.alpha))
-        return loras
+        return [LoRAModule(lora_name, leaf, child, multiplier, rank, self.alpha)
+                for leaf, lora_name, child in _discover(prefix, root_module, target_replace_modules, train_method)]
 
     # ---- flat storage ---------------------------------------------------------------------------------
     def _build_slab(self, device) -> None:
@@ -222,11 +237,7 @@ class LoRANetwork(nn.Module):
     def load_weights(self, file, strict: bool = True) -> None:
         """Inverse of `save_weights` (the reference has none): fills `lora_down` / `lora_up` from a file written by
         this package or by the reference (same key names, Appendix E); `alpha` must agree with the construction."""
-        if os.path.splitext(str(file))[1] == ".safetensors":
-            from safetensors.torch import load_file
-            sd = load_file(str(file))
-        else:
-            sd = torch.load(file, map_location="cpu", weights_only=True)
+        sd = _read_lora_file(file)
         own = self.state_dict()
         missing = [k for k in own if k.startswith("lora") and k not in sd]
         unexpected = [k for k in sd if k not in own]
@@ -247,6 +258,63 @@ class LoRANetwork(nn.Module):
     def needs_repack(self) -> bool:
         """True when the packed MFMA operand images are older than the parameters."""
         return self._packed_version != self.version
+
+    # ---- sampling: per-sample strengths, construction from a file -----------------------------------------
+    def set_strengths(self, strengths) -> None:
+        """Per-sample LoRA strengths for forward-only (sampling) passes: row b of a UNet batch runs at
+        ``strengths[b % len(strengths)]`` -- with classifier-free guidance `predict_noise` doubles the batch as
+        [uncond...; cond...], so the vector is tiled -- all in ONE pass over shared weights (bf16 only; the batch must be a
+        whole multiple of ``len(strengths)``).  The on / off switch stays ``multiplier`` (`with network:`); its value is not
+        applied on top.  ``None`` restores the single ``multiplier``."""
+        if strengths is not None:
+            strengths = tuple(float(v) for v in strengths)
+            if not strengths or not all(math.isfinite(v) for v in strengths):
+                raise ValueError(f"set_strengths: expected a non-empty sequence of finite floats, got {strengths}")
+        self.strengths = strengths
+        self._strengths_version += 1
+
+    @staticmethod
+    def _coverage(unet, names: set):
+        """(target_replace_modules, train_method) whose module discovery on ``unet`` gives exactly ``names``."""
+        seen = []
+        for targets in (UNET_TARGET_REPLACE_MODULE_TRANSFORMER, UNET_TARGET_REPLACE_MODULE_TRANSFORMER + UNET_TARGET_REPLACE_MODULE_CONV):
+            for method in ("full", "noxattn", "innoxattn", "selfattn", "xattn"):
+                found = {ln for _, ln, _ in _discover(LORA_PREFIX_UNET, unet, targets, method)}
+                if found == names:
+                    return list(targets), method
+                seen.append(len(found))
+        raise ValueError(f"the file's {len(names)} LoRA modules match no (network type, train_method) coverage of this UNet "
+                         f"(candidates have {sorted(set(seen))} modules)")
+
+    @classmethod
+    def from_file(cls, unet, path, multiplier: float = 1.0, rank: Optional[int] = None, alpha: Optional[float] = None,
+                  **kwargs) -> "LoRANetwork":
+        """A network built FROM a saved file (this package's `save_weights` or the reference's: same keys): rank =
+        ``lora_down.weight.shape[0]``, alpha and the coverage (lierla / c3lier targets, ``train_method``) are read from the
+        file's keys and tensors, then the weights are loaded.  One rank for the whole file (a convolution narrower than the
+        rank keeps its clamped ``min(rank, in, out)``, lora.py:72-74); anything else raises ValueError.  ``rank`` / ``alpha``
+        override what the file says (`load_weights` then raises where they contradict it)."""
+        sd = _read_lora_file(path)
+        ranks = {k[:-len(".lora_down.weight")]: int(v.shape[0]) for k, v in sd.items() if k.endswith(".lora_down.weight")}
+        if not ranks:
+            raise ValueError(f"{path}: no `<module>.lora_down.weight` keys")
+        alphas = {k[:-len(".alpha")]: float(v) for k, v in sd.items() if k.endswith(".alpha")}
+        detected = max(ranks.values())
+        first = next(n for n, r in ranks.items() if r == detected)
+        rank = detected if rank is None else rank
+        alpha = alphas.get(first, float(detected)) if alpha is None else alpha
+        targets, method = cls._coverage(unet, set(ranks))
+        import contextlib
+        import io
+        with contextlib.redirect_stdout(io.StringIO()):      # (the constructor prints its census and every clamped conv)
+            net = cls(unet, rank=rank, multiplier=multiplier, alpha=alpha, train_method=method, target_replace_modules=targets,
+                      **kwargs)
+        for lora in net.unet_loras:
+            if rank == detected and ranks[lora.lora_name] != lora.lora_dim:
+                raise ValueError(f"{path}: the ranks are not uniform: {first} has rank {rank}, {lora.lora_name} has rank "
+                                 f"{ranks[lora.lora_name]} (expected {lora.lora_dim})")
+        net.load_weights(path)
+        return net
 
     def __enter__(self):
         self.multiplier = 1.0

@@ -58,6 +58,7 @@ _SIGS = {
     "leco_step_begin": [_vp, _vp, _i32, _f32, _i64, _vp, _vp],
     "leco_step_mid": [_vp, _vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp, _vp, _i32, _vp],
     "leco_lora_pack": [_vp, _i32, _vp],
+    "leco_lora_rowscale": [_vp, _i64, _i32, _i32, _i32, _vp, _vp],
     "leco_lora_wgrad_conv": [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _f32, _i32, _i32, _i32, _i32, _i32,
                              _i32, _i32, _vp, _i64, _vp],
     "leco_rowgroup_sum": [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp],
@@ -410,6 +411,14 @@ def step_mid(src: torch.Tensor, dst_a: Optional[torch.Tensor], dst_b: Optional[t
 
 def lora_pack(sites_dev: torch.Tensor, nsites: int) -> Op:
     return Op("leco_lora_pack", (ptr(sites_dev), nsites))
+
+
+def lora_rowscale(t, ld, rows, cols, rows_per_sample, strengths, keep=None) -> Op:
+    """t[m][c] *= strengths[m // rows_per_sample] in place (bf16 [rows][cols], row stride ``ld``; ``t`` may be a raw device
+    address).  ``strengths``: fp32 DEVICE tensor [rows // rows_per_sample], read at launch / graph replay (bf16 only)."""
+    if _f32_active:
+        raise NotImplementedError("lora_rowscale (per-sample LoRA strengths) is implemented for the bf16 compute mode only")
+    return Op("leco_lora_rowscale", (ptr(t), ld, rows, cols, rows_per_sample, ptr(strengths)), keep=(t, strengths, keep))
 
 
 def lora_wgrad(p, ldp, q, ldq, g, g_sj, g_sc, m, r, cols, scale, part: Optional[torch.Tensor] = None) -> Op:

@@ -531,14 +531,28 @@ class Engine:
         net._packed_version = net.version
 
     # ---- plan construction ---------------------------------------------------------------------
-    def plan(self, B: int, h: int, w: int, need_bwd: bool = True, ws_slot: int = 0, share: int = 1, tag: Optional[str] = None) -> Plan:
+    SWEEP_TAG = "sweep"      # Engine.plan(..., strengths=True) keys its plans with this tag
+
+    def plan(self, B: int, h: int, w: int, need_bwd: bool = True, ws_slot: int = 0, share: int = 1, tag: Optional[str] = None,
+             strengths: bool = False) -> Plan:
         """``need_bwd=False`` builds a forward-only plan (no gradient buffers): used for the batched
         LoRA-off passes, which never run a backward.  ``ws_slot`` > 0 gives the plan's split-K launches a workspace of
         their own (the only mutable buffer plans share), so that its lists may run CONCURRENTLY with another plan's on a
         second stream (`FusedStep`: the batched frozen pass beside the LoRA-on target pass).  ``share`` > 1 (forward-only
         plans): the caller guarantees that the B input latents are ``share`` back-to-back copies of B / share samples at one
         timestep (``predict_noise``'s ``cat([latents] * 2)``, train_util.py:151) -- everything in front of the first use of
-        the prompt embeddings is then computed once per distinct sample (`PlanBuilder.shared_prefix`)."""
+        the prompt embeddings is then computed once per distinct sample (`PlanBuilder.shared_prefix`).  ``strengths=True``
+        (forward-only, bf16 only): the SWEEP variant -- its ``fwd_on`` list applies every LoRA site at a strength of its
+        own per sample, read from the plan buffer ``strengths`` (fp32 [B]) when the list runs (`PlanBuilder.sweep`)."""
+        if strengths:
+            if self.f32:
+                raise NotImplementedError("per-sample LoRA strengths: compute precision 'float32' is not implemented (bfloat16 "
+                                          "only; `train.precision: float32` does not extend to the sweep plans)")
+            if need_bwd or share > 1:
+                raise ValueError("per-sample LoRA strengths exist on forward-only plans without a shared prefix")
+            if self.network is None:
+                raise ValueError("per-sample LoRA strengths need an attached LoRA network")
+            tag = self.SWEEP_TAG if not tag else tag + "." + self.SWEEP_TAG
         key = (B, h, w, need_bwd) if ws_slot == 0 else (B, h, w, need_bwd, ws_slot)
         if share > 1:
             assert not need_bwd and B % share == 0
@@ -548,7 +562,7 @@ class Engine:
         if key not in self.plans:
             with ops.f32_mode(self.f32):
                 self.plans[key] = PlanBuilder(self, B, h, w, need_bwd, ws=self.workspace_slot(ws_slot), share=share,
-                                              ).build()
+                                              **({"sweep": True} if strengths else {})).build()
                 self.plans[key].key = key
         return self.plans[key]
 
@@ -585,9 +599,15 @@ class Engine:
 
 class PlanBuilder:
     def __init__(self, eng: Engine, B: int, h: int, w: int, need_bwd: bool = True, ws: Optional[torch.Tensor] = None,
-                 share: int = 1):
+                 share: int = 1, sweep: bool = False):
         self.eng, self.cfg, self.dev = eng, eng.cfg, eng.device
         self.share = share
+        # SWEEP variant (forward-only, bf16): every LoRA site of `fwd_on` takes the unfused route -- the down GEMM writes the
+        # low-rank image T, `lora_rowscale` scales the rows of sample b by strengths[b], the main launch consumes T through
+        # `a_ext` -- and the fast paths that form T inside another kernel stay off for the LoRA sites
+        self.sweep = sweep
+        assert not sweep or (not need_bwd and share == 1 and not eng.f32)
+        self.strengths: Optional[torch.Tensor] = None
         self.Bfull = B          # (self.B is lowered to B / share while the batch-shared prefix is built)
         self.ws = eng.workspace if ws is None else ws      # split-K slabs of this plan's launches
         self.B, self.h, self.w = B, h, w
@@ -705,7 +725,7 @@ class PlanBuilder:
         self._last_T = None
         if lora is not None:
             T = self._last_T = self.act(name + ".loraT", rows, lora.Rp)
-            if amode == A_PLAIN and lora.Rp == 32 and not self.eng.f32:
+            if amode == A_PLAIN and lora.Rp == 32 and not self.eng.f32 and not self.sweep:
                 # down-projection fused into the main GEMM's K sweep (T is still written: lora_up wgrad)
                 g_on = gemm_args(a0, site.w, yptr, lda=lda0, ldc=ldc, w_ext=lora.up_p, ext_k=32, ld_wext=32,
                                  t_w=lora.dn_s, t_rows=lora.R16, t_out=T.ptr, ld_tout=T.ld, **common)
@@ -716,6 +736,9 @@ class PlanBuilder:
                     kw.update(a1=xs[1].ptr, lda1=xs[1].ld, k_split=xs[0].cols)
                 g_t = gemm_args(a0, lora.dn_s, T.ptr, lda=lda0, ldc=T.ld, **kw)
                 self.f_on.append(ops.gemm(g_t, keep=(lora, xs, T), ws=self.ws))
+                if self.sweep:      # rows of sample b of T times strengths[b]: the term is linear in T, the weights stay shared
+                    assert rows % self.Bfull == 0
+                    self.f_on.append(ops.lora_rowscale(T.ptr, T.ld, rows, lora.Rp, rows // self.Bfull, self.strengths, keep=T))
                 e0 = min(lora.Rp, 64)
                 chain_after = y is not None and act == ACT_NONE
                 on_common = common
@@ -757,6 +780,8 @@ class PlanBuilder:
         if self.need_bwd or self.eng.f32 or os.environ.get("LECO_XGEMM", "1") in ("", "0"):
             return False
         if amode != A_PLAIN or len(xs) != 1 or rowbias is not None or act != ACT_NONE or site.conv3:
+            return False
+        if self.sweep and site.lora is not None:      # the kernel forms T in registers: no place to scale it per sample
             return False
         if rows > int(os.environ.get("LECO_XGEMM_MAX_M", "256")) or not ops.xgemm_supported(rows, site.n, site.k):
             return False
@@ -1100,6 +1125,8 @@ class PlanBuilder:
         names += [tname + ".proj_out", tname + ".proj_in", bname + ".attn1.qkv"]
         for nm in names:
             lo = S[nm].lora
+            if lo is not None and self.sweep:      # the stripe kernels form every T inside the launch
+                return False
             if lo is not None and (lo.Rp != 32 or (nm.endswith("ff.net.0.proj") and lo.up_pg is None)):
                 return False
         return S[bname + ".ff.net.0.proj"].geglu_ok
@@ -1195,7 +1222,8 @@ class PlanBuilder:
         a2 = self.attention(q2, kv, heads, hw, ctx.rows // self.B, bname + ".a2")
         h2 = self.gemm_fwd(S[bname + ".attn2.to_out.0"], a2, bname + ".h2", rows=rows, residual=h1)
         ff1 = S[bname + ".ff.net.0.proj"]
-        if not self.need_bwd and not eng.f32 and ff1.geglu_ok and (ff1.lora is None or (ff1.lora.Rp == 32 and ff1.lora.up_pg is not None)):
+        if not self.need_bwd and not eng.f32 and ff1.geglu_ok and (ff1.lora is None or (ff1.lora.Rp == 32 and ff1.lora.up_pg is not None
+                                                                                        and not self.sweep)):
             gg = self.ln_linear(bname + ".norm3", ff1, h2, bname + ".l3", bname + ".geglu", rows, geglu=True)
             return self.gemm_fwd(S[bname + ".ff.net.2"], gg, bname + ".h3", rows=rows, residual=h2), False
         l3 = self.layernorm(bname + ".norm3", h2, bname + ".l3")
@@ -1279,6 +1307,9 @@ class PlanBuilder:
         P.pred = self.buf("pred", (B, cfg.out_channels, h, w), torch.float32)
         P.dpred = self.buf("dpred", (B, cfg.out_channels, h, w), torch.float32, zero=True)
         ctx = TRef(P.ctx, B * 77, cfg.cross_attention_dim, name="ctx")
+        if self.sweep:      # per-sample LoRA strengths of `fwd_on`: written by the caller, read by every `lora_rowscale` launch
+            P.strengths = self.strengths = self.buf("strengths", (B,), torch.float32)
+            self.strengths.fill_(1.0)
         # -- time embedding
         tsin = self.act("t_sin", B, ch[0])
         self.both(ops.timestep_embedding(P.t_table, P.t_idx, 0, B, ch[0], tsin.t))
@@ -1516,6 +1547,28 @@ class UNet2DConditionModel(nn.Module):
             eng.refresh_lora(net.multiplier)
         return eng.plan(B, h, w, tag=tag)
 
+    def prepare_sweep(self, sample_shape) -> Plan:
+        """The SWEEP plan of this shape (`Engine.plan(strengths=True)`) with ``network.strengths`` in its strength buffer: row b
+        of the batch runs at strengths[b % len(strengths)] -- `predict_noise` doubles the batch as [uncond...; cond...], so the
+        vector is tiled.  The packed `up` images keep multiplier = 1; a change of strengths is one small host-to-device copy, no
+        re-pack and no new graph capture."""
+        B, _, h, w = sample_shape
+        eng = self.engine()
+        net = eng.network
+        vec = net.strengths
+        if B % len(vec):
+            raise ValueError(f"per-sample LoRA strengths: the UNet batch of {B} is not a whole multiple of the {len(vec)} strengths "
+                             f"{tuple(vec)} (set_strengths)")
+        plan = eng.plan(B, h, w, need_bwd=False, strengths=True)     # (raises in the fp32 compute mode, before any re-pack)
+        if net.needs_repack() or eng._pack_scale != 1.0:
+            net.sync_shadow()
+            eng.refresh_lora(1.0)
+        token = (net._strengths_version, id(net))
+        if getattr(plan, "strengths_src", None) != token:
+            plan.strengths.copy_(torch.tensor(list(vec) * (B // len(vec)), dtype=torch.float32))
+            plan.strengths_src = token
+        return plan
+
     def lora_active(self) -> bool:
         net = self.engine().network
         return net is not None and net.multiplier != 0
@@ -1548,7 +1601,8 @@ class UNet2DConditionModel(nn.Module):
         self._adopt_foreign_patches()
         eng = self.engine()
         lora_on = self.lora_active()
-        plan = self.prepare(sample.shape, lora_on)
+        sweep = lora_on and getattr(eng.network, "strengths", None) is not None
+        plan = self.prepare_sweep(sample.shape) if sweep else self.prepare(sample.shape, lora_on)
         plan.x_in.copy_(sample)
         plan.set_ctx(encoder_hidden_states)
         t = torch.as_tensor(timestep)
@@ -1558,6 +1612,9 @@ class UNet2DConditionModel(nn.Module):
             plan.text_embeds.copy_(added_cond_kwargs["text_embeds"])
             plan.time_ids.copy_(added_cond_kwargs["time_ids"].reshape(-1).to(torch.float32))
         net = eng.network
+        if sweep:      # forward-only: no autograd node
+            self._run(plan, "fwd_on")
+            return UNetOutput(plan.pred.to(sample.dtype))
         if lora_on and torch.is_grad_enabled() and net is not None and net.slab.requires_grad:
             return UNetOutput(_UNetFn.apply(net.slab, self, plan, sample.dtype))
         self._run(plan, "fwd_on" if lora_on else "fwd_off")

@@ -25,7 +25,6 @@ The tokenizer stays transformers' ``CLIPTokenizer``; there is no backward (no te
 """
 from __future__ import annotations
 
-import ctypes as C
 import json
 from dataclasses import dataclass, fields
 from typing import Dict, List, Optional, Tuple
@@ -33,7 +32,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 from torch import nn
 
-from . import hip, ops
+from . import graphs, ops
 from .hip import ACT_GELU, ACT_NONE, ACT_QUICK_GELU, gemm_args
 
 bf16 = torch.bfloat16
@@ -178,22 +177,12 @@ class CLIPPlan:
         self.keep: list = []
 
 
-def _graph_lib():
-    """The graph entry points of the library that is bound NOW (argument types are per loaded library object)."""
-    lib = hip.lib()
-    for nm, at in (("leco_graph_begin_capture", [C.c_void_p]), ("leco_graph_end_capture", [C.c_void_p, C.POINTER(C.c_void_p)]),
-                   ("leco_graph_launch", [C.c_void_p, C.c_void_p]), ("leco_graph_destroy", [C.c_void_p])):
-        fn = getattr(lib, nm)
-        fn.argtypes, fn.restype = at, C.c_int
-    return lib
-
-
-class CLIPEngine:
+class CLIPEngine(graphs.PlanEngine):
     """Packed device operands of one text encoder and its launch plans, keyed by (batch, sequence length)."""
 
     def __init__(self, model: "CLIPTextModel", device: torch.device):
-        self.cfg, self.device = model.cfg, device
-        self.plans: Dict[tuple, CLIPPlan] = {}
+        super().__init__(device)
+        self.cfg = model.cfg
         self.workspace = torch.empty(2 * 1024 * 1024, dtype=torch.float32, device=device)      # split-K partial slabs
         f32 = lambda t: t.detach().float().to(device).contiguous()      # noqa: E731
         wb = lambda t: t.detach().to(device, bf16).contiguous()          # noqa: E731
@@ -270,27 +259,17 @@ class CLIPEngine:
             p = self.plans[key] = self._build(B, S)
         return p
 
-    def release(self) -> None:
-        if self.device.type == "cuda" and not hip.is_emulated():
-            torch.cuda.synchronize()
-            lib = _graph_lib()
-            for p in self.plans.values():
-                if p.graph is not None:
-                    lib.leco_graph_destroy(p.graph)
-        self.plans.clear()
 
-
-class CLIPTextModel(nn.Module):
+class CLIPTextModel(graphs.ForwardOnlyModel):
     """transformers' ``CLIPTextModel``, forward only.  Compute is bf16 with fp32 accumulation whatever dtype the parameters
     are held in; outputs come back in that dtype."""
     _first = "last_hidden_state"
+    engine_type = CLIPEngine
 
     def __init__(self, cfg: Optional[CLIPTextConfig] = None):
-        super().__init__()
+        super().__init__(use_graphs=True)
         self.cfg = cfg or CLIPTextConfig()
         self.text_model = CLIPTextTransformer(self.cfg)
-        self.use_graphs = True
-        self._engine: Optional[CLIPEngine] = None
         self.requires_grad_(False)
 
     @property
@@ -315,7 +294,6 @@ class CLIPTextModel(nn.Module):
         if strict and unexpected:
             raise KeyError(f"CLIP text encoder: unexpected key {unexpected[0]!r}"
                            + (f" (and {len(unexpected) - 1} more)" if len(unexpected) > 1 else ""))
-        self.release()
         return missing, unexpected
 
     def set_precision(self, precision) -> "CLIPTextModel":
@@ -323,47 +301,6 @@ class CLIPTextModel(nn.Module):
             raise NotImplementedError(f"CLIP text encoder: compute precision {precision!r} is not implemented (bfloat16 only; "
                                       "`train.precision: float32` does not extend to the native text encoder)")
         return self
-
-    def _apply(self, fn, *a, **kw):
-        out = super()._apply(fn, *a, **kw)
-        self.release()          # the packed operands follow the parameters: rebuilt on the next call
-        return out
-
-    def engine(self) -> CLIPEngine:
-        if self._engine is None or self._engine.device != self.device:
-            self.release()
-            self._engine = CLIPEngine(self, self.device)
-        return self._engine
-
-    def release(self) -> None:
-        if self.__dict__.get("_engine") is not None:
-            self._engine.release()
-            self._engine = None
-
-    def _eager(self) -> bool:
-        return not (self.use_graphs and self.device.type == "cuda" and not hip.is_emulated()) or ops._TRACE_OPS
-
-    def _run(self, plan: CLIPPlan) -> None:
-        if self._eager():
-            ops.run_plan(plan.ops)
-            return
-        lib = _graph_lib()
-        cur = torch.cuda.current_stream()
-        if plan.graph is None:
-            ops.run_plan(plan.ops)      # first use: eager once (one-time kernel attributes are set outside the capture)
-            side = self.__dict__.get("_capture_stream")
-            if side is None:
-                side = self.__dict__["_capture_stream"] = torch.cuda.Stream()
-            side.wait_stream(cur)
-            sp = side.cuda_stream
-            hip.check(lib.leco_graph_begin_capture(sp), "graph begin")
-            try:
-                ops.run_plan(plan.ops, sp)
-            finally:
-                gh = C.c_void_p()
-                hip.check(lib.leco_graph_end_capture(sp, C.byref(gh)), "graph end")
-            plan.graph = gh
-        hip.check(lib.leco_graph_launch(plan.graph, cur.cuda_stream), "graph launch")
 
     def eos_positions(self, ids: torch.Tensor) -> torch.Tensor:
         """transformers' pooling rule: the first position equal to ``eos_token_id``, or argmax of the ids for the legacy

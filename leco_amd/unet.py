@@ -32,7 +32,7 @@ from typing import Dict, List, Optional, Sequence, Tuple, Union
 import torch
 import torch.nn as nn
 
-from . import hip, ops
+from . import graphs, hip, ops
 from .hip import (ACT_GEGLU, ACT_NONE, ACT_SILU, A_CONV3_S1, A_CONV3_S2, A_CONV3_TR2, A_CONV3_UP2, A_PLAIN, gemm_args)
 
 bf16 = torch.bfloat16
@@ -581,11 +581,7 @@ class Engine:
         if plan is None:
             return
         if plan.graphs:
-            if self.device.type == "cuda":
-                torch.cuda.synchronize(self.device)
-            lib = _graph_api()
-            for g in plan.graphs.values():
-                lib.leco_graph_destroy(g)
+            graphs.destroy(self.device, plan.graphs.values())
             plan.graphs.clear()
         plan.lists.clear()
         plan.bufs.clear()
@@ -1410,20 +1406,7 @@ class PlanBuilder:
 # =============================================================================================
 # public module
 # =============================================================================================
-_GRAPH_API_DECLARED = False
-
-
-def _graph_api():
-    global _GRAPH_API_DECLARED
-    lib = hip.lib()
-    if not _GRAPH_API_DECLARED:
-        for nm, at in [("leco_graph_begin_capture", [C.c_void_p]),
-                       ("leco_graph_end_capture", [C.c_void_p, C.POINTER(C.c_void_p)]),
-                       ("leco_graph_launch", [C.c_void_p, C.c_void_p]), ("leco_graph_destroy", [C.c_void_p])]:
-            getattr(lib, nm).argtypes = at
-            getattr(lib, nm).restype = C.c_int
-        _GRAPH_API_DECLARED = True
-    return lib
+_graph_api = graphs.api      # (bench.py imports this name)
 
 
 class _UNetFn(torch.autograd.Function):
@@ -1511,7 +1494,7 @@ class UNet2DConditionModel(nn.Module):
     # ---- execution ----------------------------------------------------------------------------------
     def _run(self, plan: Plan, which: str) -> None:
         oplist = plan.lists[which]
-        if not (self.use_graphs and self.device.type == "cuda" and not hip.is_emulated()) or ops._TRACE_OPS:
+        if not graphs.enabled(self):
             ops.run_plan(oplist)
             return
         import os
@@ -1519,24 +1502,7 @@ class UNet2DConditionModel(nn.Module):
         if eager and any(e == which.split("@")[0] or e == f"{which.split('@')[0]}:{plan.key[0]}" for e in eager.split(",")):
             ops.run_plan(oplist)
             return
-        lib = _graph_api()
-        g = plan.graphs.get(which)
-        cur = torch.cuda.current_stream()
-        if g is None:
-            import os
-            side = getattr(self, "_capture_stream", None)
-            if side is None:
-                side = self._capture_stream = torch.cuda.Stream()
-            side.wait_stream(cur)
-            sp = side.cuda_stream
-            hip.check(lib.leco_graph_begin_capture(sp), "graph begin")
-            try:
-                ops.run_plan(oplist, sp)
-            finally:
-                gh = C.c_void_p()
-                hip.check(lib.leco_graph_end_capture(sp, C.byref(gh)), "graph end")
-            g = plan.graphs[which] = gh
-        hip.check(lib.leco_graph_launch(g, cur.cuda_stream), "graph launch")
+        graphs.launch(self, plan.graphs, which, oplist, warm=False)      # (`denoise` is not idempotent: no eager warm-up)
 
     def prepare(self, sample_shape, lora_on: bool, tag: Optional[str] = None) -> Plan:
         B, _, h, w = sample_shape

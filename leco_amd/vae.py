@@ -27,7 +27,6 @@ The encoder (``encoder.conv_in``, ``encoder.down_blocks.N.resnets.M``, ``encoder
 """
 from __future__ import annotations
 
-import ctypes as C
 import json
 import struct
 import zlib
@@ -37,7 +36,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 from torch import nn
 
-from . import hip, ops
+from . import graphs, hip, ops
 from .hip import ACT_NONE, ACT_SILU, A_CONV3_S1, A_CONV3_S2_PAD01, A_CONV3_UP2, A_PLAIN, gemm_args
 
 bf16 = torch.bfloat16
@@ -397,21 +396,12 @@ class _Builder:
         return plan
 
 
-def _graph_lib():
-    """The graph entry points of the library that is bound NOW (argument types are per loaded library object)."""
-    lib = hip.lib()
-    for nm, at in (("leco_graph_begin_capture", [C.c_void_p]), ("leco_graph_end_capture", [C.c_void_p, C.POINTER(C.c_void_p)]),
-                   ("leco_graph_launch", [C.c_void_p, C.c_void_p]), ("leco_graph_destroy", [C.c_void_p])):
-        fn = getattr(lib, nm)
-        fn.argtypes, fn.restype = at, C.c_int
-    return lib
-
-
-class VAEEngine:
+class VAEEngine(graphs.PlanEngine):
     """Packed device operands of one AutoencoderKL and its launch plans, keyed by (batch, h, w)."""
 
     def __init__(self, vae: "AutoencoderKL", device: torch.device):
-        self.vae, self.cfg, self.device = vae, vae.cfg, device
+        super().__init__(device)
+        self.vae, self.cfg = vae, vae.cfg
         cfg = self.cfg
         if cfg.out_channels != 3:
             raise ValueError(f"VAE decoder: out_channels = {cfg.out_channels}, the image epilogue writes RGB")
@@ -421,7 +411,6 @@ class VAEEngine:
                              f"{WIDE_HEAD_DIMS}")
         if any(c % 32 for c in cfg.block_out_channels):
             raise ValueError("VAE decoder: block_out_channels must be multiples of 32")
-        self.plans: Dict[tuple, VAEPlan] = {}
         self.workspace = torch.empty(8 * 1024 * 1024, dtype=torch.float32, device=device)    # split-K partial slabs
         f32 = lambda t: t.detach().float().to(device).contiguous()      # noqa: E731
         self.gemm_w: Dict[str, Tuple[torch.Tensor, Optional[torch.Tensor]]] = {}
@@ -469,24 +458,16 @@ class VAEEngine:
             p = self.plans[key] = _Builder(self, B, h, w).build()
         return p
 
-    def release(self) -> None:
-        if self.device.type == "cuda" and not hip.is_emulated():
-            torch.cuda.synchronize()
-            lib = _graph_lib()
-            for p in self.plans.values():
-                if p.graph is not None:
-                    lib.leco_graph_destroy(p.graph)
-        self.plans.clear()
 
-
-class AutoencoderKL(nn.Module):
+class AutoencoderKL(graphs.ForwardOnlyModel):
     """diffusers' ``AutoencoderKL``.  The decoder half is always built; ``encoder=True`` adds ``encoder`` and ``quant_conv``
     (after the decoder, so the decoder-only module tree and ``state_dict()`` are a prefix of the full one).  `decode` takes
     the sampler's latents as they are and divides by ``config.scaling_factor`` itself; `encode` follows diffusers (no
     scaling factor), `encode_to_latents` returns scaled latents."""
+    engine_type = VAEEngine
 
     def __init__(self, cfg: Optional[VAEConfig] = None, encoder: bool = False):
-        super().__init__()
+        super().__init__(use_graphs=False)
         self.cfg = cfg or VAEConfig()
         self.post_quant_conv = nn.Conv2d(self.cfg.latent_channels, self.cfg.latent_channels, 1)
         self.decoder = Decoder(self.cfg)
@@ -498,8 +479,6 @@ class AutoencoderKL(nn.Module):
                                  "(8 moment channels)")
             self.encoder = Encoder(self.cfg)
             self.quant_conv = nn.Conv2d(2 * self.cfg.latent_channels, 2 * self.cfg.latent_channels, 1)
-        self.use_graphs = False
-        self._engine: Optional[VAEEngine] = None
         self.requires_grad_(False)
 
     @property
@@ -516,38 +495,6 @@ class AutoencoderKL(nn.Module):
             raise NotImplementedError(f"VAE decoder: compute precision {precision!r} is not implemented (bfloat16 only; "
                                       "`train.precision: float32` does not extend to the decoder)")
         return self
-
-    def engine(self) -> VAEEngine:
-        if self._engine is None or self._engine.device != self.device:
-            self._engine = VAEEngine(self, self.device)
-        return self._engine
-
-    def release(self) -> None:
-        if self._engine is not None:
-            self._engine.release()
-            self._engine = None
-
-    def _run(self, plan: VAEPlan) -> None:
-        if not (self.use_graphs and self.device.type == "cuda" and not hip.is_emulated()) or ops._TRACE_OPS:
-            ops.run_plan(plan.ops)
-            return
-        lib = _graph_lib()
-        cur = torch.cuda.current_stream()
-        if plan.graph is None:
-            ops.run_plan(plan.ops)      # first use: eager once (one-time kernel attributes are set outside the capture)
-            side = self.__dict__.get("_capture_stream")
-            if side is None:
-                side = self.__dict__["_capture_stream"] = torch.cuda.Stream()
-            side.wait_stream(cur)
-            sp = side.cuda_stream
-            hip.check(lib.leco_graph_begin_capture(sp), "graph begin")
-            try:
-                ops.run_plan(plan.ops, sp)
-            finally:
-                gh = C.c_void_p()
-                hip.check(lib.leco_graph_end_capture(sp, C.byref(gh)), "graph end")
-            plan.graph = gh
-        hip.check(lib.leco_graph_launch(plan.graph, cur.cuda_stream), "graph launch")
 
     def _decode(self, latents: torch.Tensor) -> VAEPlan:
         if latents.ndim != 4 or latents.shape[1] != self.cfg.latent_channels:

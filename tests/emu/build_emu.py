@@ -17,7 +17,7 @@ CLANG = "/opt/rocm/lib/llvm/bin/clang++"
 def sources():
     srcs = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))
             if f.endswith(".hip") and f != "runtime.hip"]
-    srcs += [os.path.join(CSRC, "common.cpp"), os.path.join(HERE, "emu_runtime.cpp")]
+    srcs += [os.path.join(CSRC, "common.cpp"), os.path.join(HERE, "emu_runtime.cpp"), os.path.join(HERE, "emu_graph_stubs.cpp")]
     return srcs
 
 

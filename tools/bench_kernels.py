@@ -1,16 +1,14 @@
 """Per-kernel microbenchmarks at the SD1.5 / 512^2 / B=4 shapes.
 Run on the GPU box: python tools/bench_kernels.py [--json out.json]"""
 import argparse
-import ctypes as C
 import json
 import os
 import sys
-import time
 
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from leco_amd import hip, ops  # noqa: E402
+from leco_amd import graphs, hip, ops  # noqa: E402
 
 bf = torch.bfloat16
 dev = torch.device("cuda:0")
@@ -120,39 +118,15 @@ def main():
     print(f"geglu L0: {t*1e6:8.1f} us  {3*M*1280*2/t/1e9:8.1f} GB/s", flush=True)
     res.append(dict(kernel="geglu_fwd", ms=t * 1e3, gbps=3 * M * 1280 * 2 / t / 1e9))
 
-    # hipGraph capture smoke: 20 small GEMMs captured on a side stream, replayed
-    lib = hip.lib()
-    for nm, at in [("leco_graph_begin_capture", [C.c_void_p]), ("leco_graph_end_capture", [C.c_void_p, C.POINTER(C.c_void_p)]),
-                   ("leco_graph_launch", [C.c_void_p, C.c_void_p]), ("leco_graph_destroy", [C.c_void_p])]:
-        getattr(lib, nm).argtypes = at
-        getattr(lib, nm).restype = C.c_int
-    st = torch.cuda.Stream()
+    # hipGraph capture smoke: 20 small GEMMs captured on a side stream, replayed (the output is what the replays wrote)
     a_ = torch.randn(256, 320, device=dev).to(bf); w_ = torch.randn(320, 320, device=dev).to(bf)
     o_ = torch.zeros(256, 320, dtype=bf, device=dev)
     g = hip.gemm_args(a_, w_, o_, m=256, n=320, k=320)
+    chain = [ops.gemm(g, keep=(a_, w_, o_), split_k=1)] * 20
+    tg = graphs.replay_us(chain, reps=50, warm=1) * 1e-6
     torch.cuda.synchronize()
-    with torch.cuda.stream(st):
-        sp = st.cuda_stream
-        hip.check(lib.leco_graph_begin_capture(sp), "begin")
-        for _ in range(20):
-            hip.gemm(g, sp)
-        gh = C.c_void_p()
-        hip.check(lib.leco_graph_end_capture(sp, C.byref(gh)), "end")
-        o_.zero_()
-        hip.check(lib.leco_graph_launch(gh, sp), "launch")
-        st.synchronize()
-        ok = torch.allclose(o_.float(), (a_.float() @ w_.float().T).to(bf).float(), rtol=2e-2, atol=2e-2)
-        t0 = time.perf_counter()
-        for _ in range(50):
-            lib.leco_graph_launch(gh, sp)
-        st.synchronize()
-        tg = (time.perf_counter() - t0) / 50
-        t0 = time.perf_counter()
-        for _ in range(50):
-            for _ in range(20):
-                hip.gemm(g, sp)
-        st.synchronize()
-        te = (time.perf_counter() - t0) / 50
+    ok = torch.allclose(o_.float(), (a_.float() @ w_.float().T).to(bf).float(), rtol=2e-2, atol=2e-2)
+    te = timeit(lambda: ops.run_plan(chain), iters=50, warm=1)
     print(f"hipGraph: correct={ok} 20-gemm graph replay {tg*1e6:.1f} us vs eager ctypes {te*1e6:.1f} us", flush=True)
     res.append(dict(kernel="graph20", graph_us=tg * 1e6, eager_us=te * 1e6, ok=bool(ok)))
     if a.json:

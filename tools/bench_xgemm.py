@@ -2,7 +2,6 @@
 the denoising pass, LoRA rank 4 fused, with residual: HIP events around back-to-back launches, both captured into ONE hipGraph
 each (no eager launch floor).  LECO_XGEMM_VAR selects the kernel variant.
     python tools/bench_xgemm.py"""
-import ctypes as C
 import math
 import os
 import sys
@@ -11,31 +10,13 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from leco_amd import hip, ops          # noqa: E402
-from leco_amd.unet import _graph_api   # noqa: E402
+from leco_amd import graphs, hip, ops  # noqa: E402
 
 bf = torch.bfloat16
 
 
 def graph_us(chain, reps=20):
-    lib = _graph_api()
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    hip.check(lib.leco_graph_begin_capture(side.cuda_stream), "begin")
-    ops.run_plan(chain, side.cuda_stream)
-    g = C.c_void_p()
-    hip.check(lib.leco_graph_end_capture(side.cuda_stream, C.byref(g)), "end")
-    cur = torch.cuda.current_stream().cuda_stream
-    for _ in range(3):
-        lib.leco_graph_launch(g, cur)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        lib.leco_graph_launch(g, cur)
-    e1.record()
-    e1.synchronize()
-    lib.leco_graph_destroy(g)
-    return e0.elapsed_time(e1) / reps / len(chain) * 1e3
+    return graphs.replay_us(chain, reps) / len(chain)
 
 
 def main():

@@ -1,6 +1,7 @@
 """In-tree build of ``libleco_hip.so`` (hipcc, gfx950 only).  Cross-compiles without a GPU."""
 from __future__ import annotations
 
+import glob
 import hashlib
 import os
 import subprocess
@@ -20,11 +21,14 @@ def _sources():
     return [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".cpp"))]
 
 
+def _headers():
+    """Every header a translation unit can include: a new or edited one can never be left out of an object's key."""
+    return sorted(glob.glob(os.path.join(ROOT, "include", "*.h")) + glob.glob(os.path.join(CSRC, "**", "*.h"), recursive=True))
+
+
 def _digest(src: str) -> str:
     h = hashlib.sha1(" ".join(FLAGS).encode())
-    deps = [src, os.path.join(ROOT, "include", "leco_hip.h"), os.path.join(CSRC, "common.h"), os.path.join(CSRC, "act.h"),
-            os.path.join(CSRC, "prims", "leco_prims.h")]
-    for d in deps:
+    for d in [src, *_headers()]:
         with open(d, "rb") as f:
             h.update(f.read())
     return h.hexdigest()[:16]

@@ -10,7 +10,8 @@
 //     image / transposed stride 2).  Cin % 64 == 0 so a 64-wide K tile never straddles a tap.
 //   * the rank-r LoRA product is one extra K tile (A_ext = x*down^T, W_ext = scale*up), so
 //     it is accumulated in fp32 inside the same MFMA accumulator (lora.py:102-106).
-//   * epilogue: + bias[n] + rowbias[sample][n] (time embedding) + residual, SiLU, bf16 store.
+//   * epilogue: + bias[n] + rowbias[sample][n] (time embedding) + residual, SiLU, bf16 store (the split-K finishing
+//     kernels below state it through epi_apply4, epilogue.h).
 //
 // Structure: 256 threads = 4 waves in a 2x2 grid over a BM x BN tile, BK = 64.  Operand tiles
 // go global -> LDS directly (global_load_lds_dwordx4, no VGPR staging, no ds_write): each wave
@@ -33,8 +34,8 @@
 #include <hip/hip_runtime.h>
 #include <leco_prims.h>
 
-#include "act.h"
 #include "common.h"
+#include "epilogue.h"
 
 namespace leco {
 namespace {
@@ -623,7 +624,6 @@ __global__ __launch_bounds__(NWM * 128) void gemm_kernel(const leco_gemm_args p,
 __global__ __launch_bounds__(256) void splitk_finish_kernel(const leco_gemm_args p, const float* ws, int splits) {
     const int M = p.m, N = p.n, nq = N / 4;
     const int64_t total = (int64_t)M * nq;
-    bf16_t* cp = (bf16_t*)p.c;
     const bf16_t* res = (const bf16_t*)p.residual;
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
         const int m = (int)(e / nq), n = (int)(e - (int64_t)m * nq) * 4;
@@ -633,28 +633,9 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(const leco_gemm_args
             a[0] += b[0]; a[1] += b[1]; a[2] += b[2]; a[3] += b[3];
         }
         float v[4] = {a[0], a[1], a[2], a[3]};
-        if (p.bias) {
-            f32x4 b = *(const f32x4*)(p.bias + n);
-            v[0] += b[0]; v[1] += b[1]; v[2] += b[2]; v[3] += b[3];
-        }
-        if (p.rowbias) {
-            f32x4 b = *(const f32x4*)(p.rowbias + (int64_t)(m / p.rows_per_group) * p.ld_rowbias + n);
-            v[0] += b[0]; v[1] += b[1]; v[2] += b[2]; v[3] += b[3];
-        }
-        if (res) {
-            u32x2 rr = *(const u32x2*)(res + (int64_t)m * p.ldr + n);
-            v[0] += bf2f((bf16_t)(rr[0] & 0xffffu)); v[1] += bf2f((bf16_t)(rr[0] >> 16));
-            v[2] += bf2f((bf16_t)(rr[1] & 0xffffu)); v[3] += bf2f((bf16_t)(rr[1] >> 16));
-        }
-        apply_act(v, p.act);
-        if (cp) {
-            u32x2 o = {pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3])};
-            *(u32x2*)(cp + (int64_t)m * p.ldc + n) = o;
-        }
-        if (p.c_f32) {
-            f32x4 o = {v[0], v[1], v[2], v[3]};
-            *(f32x4*)(p.c_f32 + (int64_t)m * p.ldc32 + n) = o;
-        }
+        u32x2 rr = {0u, 0u};
+        if (res) rr = *(const u32x2*)(res + (int64_t)m * p.ldr + n);
+        epi_apply4(p, m, n, v, rr);
     }
 }
 
@@ -669,7 +650,6 @@ __global__ __launch_bounds__(256) void splitk_finish_stats_kernel(const leco_gem
     const int m0 = (int)blockIdx.y * 64, n = (int)blockIdx.x * 64 + c4 * 4;
     const int mhi = m0 + 64 < M ? m0 + 64 : M;
     const bool single = m0 / p.stats_rows == (mhi - 1) / p.stats_rows;
-    bf16_t* cp = (bf16_t*)p.c;
     const bf16_t* res = (const bf16_t*)p.residual;
     float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
     int bcur = -1;
@@ -688,26 +668,9 @@ __global__ __launch_bounds__(256) void splitk_finish_stats_kernel(const leco_gem
                 a[0] += b[0]; a[1] += b[1]; a[2] += b[2]; a[3] += b[3];
             }
             float v[4] = {a[0], a[1], a[2], a[3]};
-            if (p.bias) {
-                const f32x4 b = *(const f32x4*)(p.bias + n);
-                v[0] += b[0]; v[1] += b[1]; v[2] += b[2]; v[3] += b[3];
-            }
-            if (p.rowbias) {
-                const f32x4 b = *(const f32x4*)(p.rowbias + (int64_t)(m / p.rows_per_group) * p.ld_rowbias + n);
-                v[0] += b[0]; v[1] += b[1]; v[2] += b[2]; v[3] += b[3];
-            }
-            if (res) {
-                const u32x2 rr = *(const u32x2*)(res + (int64_t)m * p.ldr + n);
-                v[0] += bf2f((bf16_t)(rr[0] & 0xffffu)); v[1] += bf2f((bf16_t)(rr[0] >> 16));
-                v[2] += bf2f((bf16_t)(rr[1] & 0xffffu)); v[3] += bf2f((bf16_t)(rr[1] >> 16));
-            }
-            apply_act(v, p.act);
-            const u32x2 o = {pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3])};
-            *(u32x2*)(cp + (int64_t)m * p.ldc + n) = o;
-            if (p.c_f32) {
-                const f32x4 of = {v[0], v[1], v[2], v[3]};
-                *(f32x4*)(p.c_f32 + (int64_t)m * p.ldc32 + n) = of;
-            }
+            u32x2 rr = {0u, 0u};
+            if (res) rr = *(const u32x2*)(res + (int64_t)m * p.ldr + n);
+            const u32x2 o = epi_apply4(p, m, n, v, rr);
             if (!single) {
                 const int b = m / p.stats_rows;
                 if (b != bcur) {

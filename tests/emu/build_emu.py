@@ -1,6 +1,7 @@
 """TEST INFRASTRUCTURE ONLY -- builds tests/emu/_build/libleco_emu.so: the *same* kernel
 sources as libleco_hip.so (leco_amd/csrc/*.hip), compiled for the host with ROCm's clang++
 against the fiber emulator in this directory, so kernel logic can be checked on a CPU."""
+import glob
 import hashlib
 import os
 import subprocess
@@ -21,11 +22,15 @@ def sources():
     return srcs
 
 
+def _headers():
+    """Every header a translation unit can include (the kernels', the ABI's and the emulator's own)."""
+    return sorted(glob.glob(os.path.join(ROOT, "include", "*.h")) + glob.glob(os.path.join(CSRC, "**", "*.h"), recursive=True)
+                  + glob.glob(os.path.join(HERE, "**", "*.h"), recursive=True))
+
+
 def _digest(path):
     h = hashlib.sha1()
-    deps = [path, os.path.join(HERE, "hip", "hip_runtime.h"), os.path.join(HERE, "leco_prims.h"),
-            os.path.join(ROOT, "include", "leco_hip.h"), os.path.join(CSRC, "common.h")]
-    for d in deps:
+    for d in [path, *_headers()]:
         with open(d, "rb") as f:
             h.update(f.read())
     return h.hexdigest()[:16]

@@ -417,6 +417,38 @@ def test_producer_side_groupnorm_statistics(dev, kind, atom):
     assert rel_err(cs.cpu(), ref) < 1e-5
 
 
+# (tile 1 takes its wave shape from the grid size and LECO_GEMM_W4_MIN_BLOCKS; 5 and 6 name the two shapes)
+_STATS_TILE_KERNEL = {1: "gemm_kernel<128, 128, false, ", 2: "gemm_kernel<128, 160, false, 4, 4, 0>",
+                      3: "gemm_kernel<64, 64, false, 4, 2, 0>", 4: "gemm_kernel<256, 128, false, 3, 4, 0>",
+                      5: "gemm_kernel<128, 128, false, 2, 2, 0>", 6: "gemm_kernel<128, 128, false, 4, 4, 0>",
+                      11: "gemm_kernel<128, 64, false, 4, 4, 0>"}
+
+
+@pytest.mark.parametrize("atom", [1, 10])
+@pytest.mark.parametrize("tile", [1, 2, 3, 4, 5, 6, 11])
+def test_gemm_col_stats_every_tile(dev, tile, atom):
+    """col_stats out of every gemm_kernel tile size and wave shape (the staged epilogue is instantiated per tile): 3 samples
+    of 100 rows, so every tile meets a round inside one sample (rows 0..63 / 0..99: the LDS fast path), a round that spans
+    samples (rows 64..127, 128..255: one pair of atomics per column and sample) and ragged last tiles (300 % 128,
+    200 % 160, 200 % 128); bias + residual + SiLU in front of the rounding; atoms of 1 and 10 columns."""
+    torch.manual_seed(17)
+    B, HW, N, K = 3, 100, 200, 128
+    M = B * HW
+    a = torch.randn(M, K).to(bf).to(dev); w = (torch.randn(N, K) / K ** 0.5).to(bf).to(dev)
+    bias = torch.randn(N).to(dev); res = torch.randn(M, N).to(bf).to(dev)
+    out = torch.zeros(M, N, dtype=bf, device=dev)
+    cs = torch.zeros(B, N // atom, 2, device=dev)
+    g = hip.gemm_args(a, w, out, m=M, n=N, k=K, bias=bias, residual=res, act=hip.ACT_SILU, col_stats=cs, stats_rows=HW,
+                      stats_atom=atom)
+    desc = hip.gemm_describe(g, tile, 1, None, 0)
+    assert _STATS_TILE_KERNEL[tile] in desc and "split=1" in desc, desc
+    hip.gemm(g, ops.default_stream(), tile=tile, split_k=1)
+    _sync(dev)
+    ref = F.silu(a.float() @ w.float().T + bias + res.float())
+    assert rel_err(out, ref) < TOLBF
+    assert rel_err(cs.cpu(), _col_stats_ref(out, B, HW, atom)) < 1e-5
+
+
 @pytest.mark.parametrize("act,B,HW,C0,C1,G,atom", [(1, 2, 70, 64, 0, 32, 2), (0, 3, 33, 64, 128, 32, 2), (1, 1, 300, 320, 0, 32, 10),
                                                    (1, 2, 16, 1280, 640, 32, 10), (0, 2, 20, 64, 0, 16, 1),
                                                    (1, 1, 11, 1280, 1280, 32, 10)])      # 320 channel vectors: two column sweeps

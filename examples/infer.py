@@ -16,6 +16,9 @@ image is encoded by the HIP VAE encoder, noised to the timestep `S` selects, and
 `--lora FILE` reads rank, alpha and coverage from the file (`--rank` / `--alpha` override).  `--lora_scales` is the slider
 sweep: one seed and one initial latent (or `--init_image`) at every strength, all strengths through each denoising step as one
 batch (`LoRANetwork.set_strengths`, bf16 only); `--image` becomes a contact sheet, left to right, `--out` holds [n,4,h,w].
+`--lora` may be repeated: the files are stacked (`LoRANetwork.from_files`), `--lora_multipliers a,b` sets one fixed multiplier
+per file, and `--lora_scales`, given once per `--lora` in the same order, samples the cross product in one batched pass (first
+file slowest; the contact sheet has the last file's strengths left to right, the other combinations top to bottom).
 """
 import argparse
 import contextlib
@@ -103,9 +106,10 @@ def main(argv=None):
     save_file({"latents": latents.float().cpu().contiguous()}, args.out,
               {"prompt": args.prompt, "steps": str(args.steps), "guidance_scale": str(args.guidance_scale)})
     print(f"Done. latents {tuple(latents.shape)} -> {args.out}")
-    if args.image:
-        (_write_image if scales is None else _lora_sweep.write_sheet)(latents, args.vae or args.model, args.image, dev,
-                                                                       use_graphs=unet.use_graphs)
+    if args.image and scales is None:
+        _write_image(latents, args.vae or args.model, args.image, dev, use_graphs=unet.use_graphs)
+    elif args.image:
+        _lora_sweep.write_sheet(latents, args.vae or args.model, args.image, dev, use_graphs=unet.use_graphs, cols=args.sheet_cols)
     return latents
 
 

@@ -147,6 +147,15 @@ int leco_lora_pack(const leco_lora_site* sites, int32_t nsites, leco_stream_t st
  * rows is a multiple of rows_per_sample; columns cols..ld are not touched. */
 int leco_lora_rowscale(void* t, int64_t ld, int32_t rows, int32_t cols, int32_t rows_per_sample, const float* strengths,
                        leco_stream_t stream);
+/* The same for a STACK of LoRA files that sit side by side in the rank dimension (LoRAStack): every file has a strength of
+ * its own per sample,
+ *     T[m][c] = bf16(float(T[m][c]) * strengths[m / rows_per_sample][col_file[c % period]]),
+ * strengths = fp32 [rows / rows_per_sample][files] and col_file = int32 [period] (entries < files), both in DEVICE memory and
+ * read when the kernel runs.  period = the per-module stacked rank (a fused q|k|v site holds three modules of `period`
+ * columns in one T); it need not be a multiple of 8 and the files' column blocks need not start on one.  1 <= files <= 8,
+ * period >= 1; cols, ld, T and rows as for leco_lora_rowscale. */
+int leco_lora_rowscale_stack(void* t, int64_t ld, int32_t rows, int32_t cols, int32_t rows_per_sample, const float* strengths,
+                             int32_t files, const int32_t* col_file, int32_t period, leco_stream_t stream);
 
 
 /* G[j*g_sj + c*g_sc] += scale * sum_m P[m][p_off+j] * Q[m][q_off+c], j<r, c<cols (LoRA weight

@@ -116,6 +116,38 @@ __global__ __launch_bounds__(256) void lora_rowscale_kernel(bf16_t* T, int64_t l
     }
 }
 
+// ---- per-sample, per-FILE LoRA strength of a stacked network (several LoRA files side by side in the rank dimension) -----
+//     T[m][c] *= S[m / rows_per_sample][col_file[c % period]],   in place, row-strided bf16
+// `period` = the per-module stacked rank R (a fused q|k|v site holds three modules of R columns in one T), col_file[R] maps
+// a column to its file.  Same traffic as `lora_rowscale_kernel`: one 16-byte load and one 16-byte store per 8 columns.  The
+// 8 columns of a vector may belong to different files and may wrap the period, so every element selects its own strength:
+// the position inside the period is computed once per vector (the only division by `period`) and stepped with a wrap; the
+// table and the sample's strength row (a few dozen bytes, shared by every lane that works on the sample) come through the
+// cache.  Both are read at every launch, so a captured graph sees what they hold at replay.  One fp32 multiply and one
+// round-to-nearest-even per element.
+__global__ __launch_bounds__(256) void lora_rowscale_stack_kernel(bf16_t* T, int64_t ld, int M, int C, int rows_per_sample,
+                                                                   const float* S, int files, const int32_t* col_file,
+                                                                   int period) {
+    const int nv = C / 8;
+    const int64_t total = (int64_t)M * nv;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+        const int r = (int)(e / nv);
+        const int col = (int)(e - (int64_t)r * nv) * 8;
+        const float* s = S + (int64_t)(r / rows_per_sample) * files;
+        int p = col % period;
+        u32x4* q = (u32x4*)(T + (int64_t)r * ld + col);
+        float x[8];
+        unpack8(*q, x);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const unsigned f = (unsigned)col_file[p];
+            x[i] *= s[f < (unsigned)files ? f : (unsigned)files - 1];      // (a bad table entry can never read outside the row)
+            if (++p == period) p = 0;
+        }
+        *q = pack8(x);
+    }
+}
+
 // ---- dgrad of nearest-2x upsample: dx[b][y][x][c] = sum of the 2x2 block of dy --------------------
 __global__ __launch_bounds__(256) void upsample_bwd_kernel(const bf16_t* dy, bf16_t* dx, int B, int H, int W,
                                                             int C) {
@@ -1156,6 +1188,22 @@ extern "C" int leco_lora_rowscale(void* t, int64_t ld, int32_t rows, int32_t col
     hipLaunchKernelGGL(lora_rowscale_kernel, dim3(grid_for((int64_t)rows * cols / 8)), dim3(256), 0, LECO_STREAM, (bf16_t*)t, ld,
                        rows, cols, rows_per_sample, strengths);
     return check_launch("leco_lora_rowscale");
+}
+extern "C" int leco_lora_rowscale_stack(void* t, int64_t ld, int32_t rows, int32_t cols, int32_t rows_per_sample,
+                                        const float* strengths, int32_t files, const int32_t* col_file, int32_t period,
+                                        leco_stream_t stream) {
+    if (!t || !strengths || rows <= 0 || cols <= 0 || rows_per_sample <= 0 || rows % rows_per_sample)
+        return fail(-EINVAL, "lora_rowscale_stack: rows=%d must be a positive multiple of rows_per_sample=%d", rows,
+                    rows_per_sample);
+    if (cols % 8 || ld % 8 || ld < cols || ((uintptr_t)t & 15))
+        return fail(-EINVAL, "lora_rowscale_stack: cols=%d, ld=%lld must be multiples of 8 (ld >= cols) and T 16-byte aligned",
+                    cols, (long long)ld);
+    if (!col_file || files < 1 || files > 8 || period < 1)
+        return fail(-EINVAL, "lora_rowscale_stack: files=%d must be in 1..8 and period=%d >= 1 (col_file: [period] entries < files)",
+                    files, period);
+    hipLaunchKernelGGL(lora_rowscale_stack_kernel, dim3(grid_for((int64_t)rows * cols / 8)), dim3(256), 0, LECO_STREAM, (bf16_t*)t,
+                       ld, rows, cols, rows_per_sample, strengths, files, col_file, period);
+    return check_launch("leco_lora_rowscale_stack");
 }
 extern "C" int leco_upsample2x_bwd(const void* dy, void* dx, int32_t batch, int32_t h, int32_t w, int32_t c,
                                    leco_stream_t stream) {

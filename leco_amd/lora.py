@@ -286,6 +286,18 @@ class LoRANetwork(nn.Module):
         raise ValueError(f"the file's {len(names)} LoRA modules match no (network type, train_method) coverage of this UNet "
                          f"(candidates have {sorted(set(seen))} modules)")
 
+    @staticmethod
+    def _scan_file(path):
+        """(state dict, {module: rank}, the file's rank, the first module that has it, the file's alpha)."""
+        sd = _read_lora_file(path)
+        ranks = {k[:-len(".lora_down.weight")]: int(v.shape[0]) for k, v in sd.items() if k.endswith(".lora_down.weight")}
+        if not ranks:
+            raise ValueError(f"{path}: no `<module>.lora_down.weight` keys")
+        alphas = {k[:-len(".alpha")]: float(v) for k, v in sd.items() if k.endswith(".alpha")}
+        detected = max(ranks.values())
+        first = next(n for n, r in ranks.items() if r == detected)
+        return sd, ranks, detected, first, alphas.get(first, float(detected))
+
     @classmethod
     def from_file(cls, unet, path, multiplier: float = 1.0, rank: Optional[int] = None, alpha: Optional[float] = None,
                   **kwargs) -> "LoRANetwork":
@@ -294,15 +306,9 @@ class LoRANetwork(nn.Module):
         file's keys and tensors, then the weights are loaded.  One rank for the whole file (a convolution narrower than the
         rank keeps its clamped ``min(rank, in, out)``, lora.py:72-74); anything else raises ValueError.  ``rank`` / ``alpha``
         override what the file says (`load_weights` then raises where they contradict it)."""
-        sd = _read_lora_file(path)
-        ranks = {k[:-len(".lora_down.weight")]: int(v.shape[0]) for k, v in sd.items() if k.endswith(".lora_down.weight")}
-        if not ranks:
-            raise ValueError(f"{path}: no `<module>.lora_down.weight` keys")
-        alphas = {k[:-len(".alpha")]: float(v) for k, v in sd.items() if k.endswith(".alpha")}
-        detected = max(ranks.values())
-        first = next(n for n, r in ranks.items() if r == detected)
+        _, ranks, detected, first, file_alpha = cls._scan_file(path)
         rank = detected if rank is None else rank
-        alpha = alphas.get(first, float(detected)) if alpha is None else alpha
+        alpha = file_alpha if alpha is None else alpha
         targets, method = cls._coverage(unet, set(ranks))
         import contextlib
         import io
@@ -325,6 +331,161 @@ class LoRANetwork(nn.Module):
         self.multiplier = 0
         for lora in self.unet_loras:
             lora.multiplier = 0
+
+
+    @staticmethod
+    def from_files(unet, paths, multipliers=None, **kwargs) -> "LoRAStack":
+        """Several saved LoRA files as ONE network (`LoRAStack`): the files sit side by side in the rank dimension."""
+        return LoRAStack(unet, paths, multipliers, **kwargs)
+
+
+def _union_coverage(unet, names: set):
+    """The smallest discoverable (target_replace_modules, train_method) whose module set contains ``names``."""
+    best = None
+    for targets in (UNET_TARGET_REPLACE_MODULE_TRANSFORMER, UNET_TARGET_REPLACE_MODULE_TRANSFORMER + UNET_TARGET_REPLACE_MODULE_CONV):
+        for method in ("full", "noxattn", "innoxattn", "selfattn", "xattn"):
+            found = {ln: child for _, ln, child in _discover(LORA_PREFIX_UNET, unet, targets, method)}
+            if names <= set(found) and (best is None or len(found) < len(best[2])):
+                best = (list(targets), method, found)
+    if best is None:
+        raise ValueError(f"the files' {len(names)} LoRA modules fit no (network type, train_method) coverage of this UNet, "
+                         f"e.g. {sorted(names)[0]}")
+    return best
+
+
+class LoRAStack(LoRANetwork):
+    """F >= 1 LoRA files combined into one ordinary network for SAMPLING (`LoRANetwork.from_files`): the engine attaches,
+    packs and runs it like a single-file network of rank R = sum of the files' ranks r_j.
+
+    Column layout, the same in every module: file j owns columns ``off_j .. off_j + r_j`` of the rank dimension, ``off_j =
+    r_0 + ... + r_(j-1)`` (`col_file`: column -> file).  The rows of `lora_down` in that block are file j's `lora_down` (zero
+    where the file does not cover the module); the columns of `lora_up` are ``alpha_j / r_j . lora_up_j`` -- the files'
+    scales differ, the packed operand images of a GEMM site carry ONE, so each file's own scale is folded into its block (in
+    fp32, before the bf16 shadow is made) and the network is built with ``alpha = R``: a network-level scale of 1.  (One
+    file: the network keeps the file's alpha and its `lora_up` as it is -- the same slab as `from_file`.)
+
+    `set_multipliers`: one FIXED multiplier per file, folded into the `lora_up` blocks (a re-pack, no new plan or graph).
+    `set_strengths`: per-SAMPLE rows of F strengths for the forward-only sweep plans (bf16 only); the blocks then carry only
+    ``alpha_j / r_j``.  ``multiplier`` / ``with stack:`` stay the on / off switch.  `save_weights` writes the merged rank-R
+    network (alpha = R, the multipliers folded in): a normal LoRA file."""
+
+    def __init__(self, unet, paths, multipliers=None, **kwargs) -> None:
+        paths = [paths] if isinstance(paths, (str, os.PathLike)) else list(paths)
+        if not paths:
+            raise ValueError("LoRANetwork.from_files: no files given")
+        scans = [self._scan_file(p) for p in paths]
+        file_ranks = [sc[2] for sc in scans]
+        R = sum(file_ranks)
+        # one file keeps its own alpha; several get alpha = R (network scale 1) and their own alpha / r inside `lora_up`
+        net_alpha = float(scans[0][4]) if len(paths) == 1 else float(R)
+        names = set().union(*(set(sc[1]) for sc in scans))
+        targets, method, found = _union_coverage(unet, names)
+        for ln, child in found.items():
+            conv = child.__class__.__name__ == "Conv2d"
+            width = min(child.in_channels, child.out_channels) if conv else min(child.in_features, child.out_features)
+            if R > width:
+                raise ValueError(f"LoRANetwork.from_files: the stacked rank {R} (= {' + '.join(map(str, file_ranks))}) is wider than "
+                                 f"{ln} ({width} channels)")
+        import contextlib
+        import io
+        kwargs.setdefault("multiplier", 1.0)
+        with contextlib.redirect_stdout(io.StringIO()):      # (the constructor prints its census)
+            super().__init__(unet, rank=R, alpha=net_alpha, train_method=method, target_replace_modules=targets, **kwargs)
+        self.paths = [str(p) for p in paths]
+        self.file_ranks = file_ranks
+        self.file_alphas = [float(sc[4]) for sc in scans]
+        self.col_file = [j for j, r in enumerate(file_ranks) for _ in range(r)]
+        with torch.no_grad():
+            off = 0
+            for path, (sd, ranks, r_file, first, alpha), j in zip(paths, scans, range(len(paths))):
+                for lora in self.unet_loras:
+                    dn, up = lora.lora_down.weight, lora.lora_up.weight
+                    if off == 0:
+                        dn.zero_(); up.zero_()
+                    if lora.lora_name not in ranks:
+                        continue
+                    # a convolution narrower than the file's rank keeps its clamped min(rank, in, out) (lora.py:72-74)
+                    r_mod = min(r_file, dn.shape[1], up.shape[0]) if dn.ndim == 4 else r_file
+                    if ranks[lora.lora_name] != r_mod:
+                        raise ValueError(f"{path}: the ranks are not uniform: {first} has rank {r_file}, {lora.lora_name} has rank "
+                                         f"{ranks[lora.lora_name]} (expected {r_mod})")
+                    fd = sd[lora.lora_name + ".lora_down.weight"].float()
+                    fu = sd[lora.lora_name + ".lora_up.weight"].float()
+                    scale = (alpha / r_mod) / (net_alpha / R)
+                    dn[off:off + r_mod].copy_(fd.reshape(dn[off:off + r_mod].shape))
+                    up[:, off:off + r_mod].copy_((fu if scale == 1.0 else fu * scale).reshape(up[:, off:off + r_mod].shape))
+                off += r_file
+        self._base = self.slab.detach().clone()      # the blocks at multiplier 1: what `_fold` scales
+        self._folded = (1.0,) * len(paths)
+        self.multipliers = self._folded
+        self.mark_updated()
+        self.sync_shadow()
+        if multipliers is not None:
+            self.set_multipliers(multipliers)
+
+    def _fold(self, mults) -> None:
+        """lora_up block j = its multiplier-1 image times mults[j] (fp32; the bf16 shadow and the packed operands follow at the
+        next LoRA-on pass)."""
+        mults = tuple(mults)
+        if mults == self._folded:
+            return
+        if self._base.device != self.slab.device:
+            self._base = self._base.to(self.slab.device)
+        with torch.no_grad():
+            self.slab.detach().copy_(self._base)
+            per_col = torch.tensor([mults[j] for j in self.col_file], dtype=torch.float32, device=self.slab.device)
+            for lora in self.unet_loras:
+                up = lora.lora_up.weight
+                up.mul_(per_col.view(1, -1, *([1] * (up.ndim - 2))))
+        self._folded = mults
+        self.mark_updated()
+
+    def set_multipliers(self, multipliers) -> None:
+        """One fixed multiplier per file (default: all 1) for the ordinary, non-sweep passes."""
+        mults = tuple(float(v) for v in multipliers)
+        if len(mults) != len(self.file_ranks) or not all(math.isfinite(v) for v in mults):
+            raise ValueError(f"set_multipliers: expected {len(self.file_ranks)} finite floats (one per file), got {mults}")
+        self.multipliers = mults
+        if self.strengths is None:
+            self._fold(mults)
+
+    def set_strengths(self, rows) -> None:
+        """Per-sample strengths, one ROW of F floats per sample: row b of a UNet batch runs file j at ``rows[b % len(rows)][j]``
+        (tiled over the CFG-doubled batch; the batch must be a whole multiple of ``len(rows)``), in ONE forward-only pass
+        (bf16 only).  One file: plain floats are accepted too.  The fixed multipliers are not applied on top; ``None``
+        restores them."""
+        F = len(self.file_ranks)
+        if rows is None:
+            self.strengths = None
+            self._strengths_version += 1
+            self._fold(self.multipliers)
+            return
+        out = []
+        for row in rows:
+            if isinstance(row, (int, float)):
+                if F != 1:
+                    raise ValueError(f"set_strengths: a stack of {F} files takes one tuple of {F} strengths per sample, got the "
+                                     f"plain number {row}")
+                row = (row,)
+            row = tuple(float(v) for v in row)
+            if len(row) != F:
+                raise ValueError(f"set_strengths: expected {F} strengths per sample (one per file), got {row}")
+            out.append(row)
+        if not out or not all(math.isfinite(v) for row in out for v in row):
+            raise ValueError(f"set_strengths: expected a non-empty sequence of rows of finite floats, got {out}")
+        self.strengths = tuple(out)
+        self._strengths_version += 1
+        self._fold((1.0,) * F)
+
+    def save_weights(self, file, dtype=None, metadata: Optional[dict] = None):
+        """The merged network: rank R, alpha = R (one file: that file's alpha), the current multipliers folded into
+        `lora_up` -- a normal LoRA file that `LoRANetwork.from_file` loads."""
+        held = self._folded
+        self._fold(self.multipliers)
+        try:
+            super().save_weights(file, dtype, metadata)
+        finally:
+            self._fold(held)
 
 
 class _ForeignModuleView:

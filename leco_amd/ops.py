@@ -59,6 +59,7 @@ _SIGS = {
     "leco_step_mid": [_vp, _vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp, _vp, _i32, _vp],
     "leco_lora_pack": [_vp, _i32, _vp],
     "leco_lora_rowscale": [_vp, _i64, _i32, _i32, _i32, _vp, _vp],
+    "leco_lora_rowscale_stack": [_vp, _i64, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp],
     "leco_lora_wgrad_conv": [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _f32, _i32, _i32, _i32, _i32, _i32,
                              _i32, _i32, _vp, _i64, _vp],
     "leco_rowgroup_sum": [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp],
@@ -419,6 +420,22 @@ def lora_rowscale(t, ld, rows, cols, rows_per_sample, strengths, keep=None) -> O
     if _f32_active:
         raise NotImplementedError("lora_rowscale (per-sample LoRA strengths) is implemented for the bf16 compute mode only")
     return Op("leco_lora_rowscale", (ptr(t), ld, rows, cols, rows_per_sample, ptr(strengths)), keep=(t, strengths, keep))
+
+
+def lora_rowscale_stack(t, ld, rows, cols, rows_per_sample, strengths, files, col_file, period, keep=None) -> Op:
+    """t[m][c] *= strengths[m // rows_per_sample][col_file[c % period]] in place: `lora_rowscale` for a stack of ``files``
+    LoRA files (`LoRAStack`).  ``strengths``: fp32 DEVICE tensor [rows // rows_per_sample][files]; ``col_file``: int32 DEVICE
+    tensor [period] (column of a module -> file), or a host list, which is checked and copied to the device of ``strengths``.
+    Both are read at launch / graph replay (bf16 only)."""
+    if _f32_active:
+        raise NotImplementedError("lora_rowscale_stack (per-sample LoRA strengths) is implemented for the bf16 compute mode only")
+    if not isinstance(col_file, torch.Tensor):
+        table = [int(v) for v in col_file]
+        if len(table) != period or any(v < 0 or v >= files for v in table):
+            raise ValueError(f"lora_rowscale_stack: col_file must hold period={period} entries in 0..{files - 1}, got {table}")
+        col_file = torch.tensor(table, dtype=torch.int32, device=strengths.device)
+    return Op("leco_lora_rowscale_stack", (ptr(t), ld, rows, cols, rows_per_sample, ptr(strengths), files, ptr(col_file), period),
+              keep=(t, strengths, col_file, keep))
 
 
 def lora_wgrad(p, ldp, q, ldq, g, g_sj, g_sc, m, r, cols, scale, part: Optional[torch.Tensor] = None) -> Op:

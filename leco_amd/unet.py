@@ -530,6 +530,16 @@ class Engine:
             ops.lora_pack(self._pack_dev, len(self.lora_sites)).run()
         net._packed_version = net.version
 
+    def stack_col_file(self) -> Optional[torch.Tensor]:
+        """Device copy (int32 [R]) of the column -> file table of an attached `LoRAStack`; None for any other network."""
+        table = getattr(self.network, "col_file", None)
+        if table is None:
+            return None
+        held = self.__dict__.get("_col_file_dev")
+        if held is None or held[0] is not self.network:
+            held = self._col_file_dev = (self.network, torch.tensor(table, dtype=torch.int32, device=self.device))
+        return held[1]
+
     # ---- plan construction ---------------------------------------------------------------------
     SWEEP_TAG = "sweep"      # Engine.plan(..., strengths=True) keys its plans with this tag
 
@@ -543,7 +553,8 @@ class Engine:
         timestep (``predict_noise``'s ``cat([latents] * 2)``, train_util.py:151) -- everything in front of the first use of
         the prompt embeddings is then computed once per distinct sample (`PlanBuilder.shared_prefix`).  ``strengths=True``
         (forward-only, bf16 only): the SWEEP variant -- its ``fwd_on`` list applies every LoRA site at a strength of its
-        own per sample, read from the plan buffer ``strengths`` (fp32 [B]) when the list runs (`PlanBuilder.sweep`)."""
+        own per sample, read from the plan buffer ``strengths`` (fp32 [B]; [B][F] for a `LoRAStack` of F files) when the list runs
+        (`PlanBuilder.sweep`)."""
         if strengths:
             if self.f32:
                 raise NotImplementedError("per-sample LoRA strengths: compute precision 'float32' is not implemented (bfloat16 "
@@ -604,6 +615,7 @@ class PlanBuilder:
         self.sweep = sweep
         assert not sweep or (not need_bwd and share == 1 and not eng.f32)
         self.strengths: Optional[torch.Tensor] = None
+        self.col_file: Optional[torch.Tensor] = None      # (sweep plans of a `LoRAStack`: column -> file, see `build`)
         self.Bfull = B          # (self.B is lowered to B / share while the batch-shared prefix is built)
         self.ws = eng.workspace if ws is None else ws      # split-K slabs of this plan's launches
         self.B, self.h, self.w = B, h, w
@@ -734,7 +746,11 @@ class PlanBuilder:
                 self.f_on.append(ops.gemm(g_t, keep=(lora, xs, T), ws=self.ws))
                 if self.sweep:      # rows of sample b of T times strengths[b]: the term is linear in T, the weights stay shared
                     assert rows % self.Bfull == 0
-                    self.f_on.append(ops.lora_rowscale(T.ptr, T.ld, rows, lora.Rp, rows // self.Bfull, self.strengths, keep=T))
+                    if self.col_file is None:
+                        self.f_on.append(ops.lora_rowscale(T.ptr, T.ld, rows, lora.Rp, rows // self.Bfull, self.strengths, keep=T))
+                    else:           # a stack of files: the columns of file j of sample b times strengths[b][j]
+                        self.f_on.append(ops.lora_rowscale_stack(T.ptr, T.ld, rows, lora.Rp, rows // self.Bfull, self.strengths,
+                                                                 self.strengths.shape[1], self.col_file, lora.r, keep=T))
                 e0 = min(lora.Rp, 64)
                 chain_after = y is not None and act == ACT_NONE
                 on_common = common
@@ -1304,7 +1320,10 @@ class PlanBuilder:
         P.dpred = self.buf("dpred", (B, cfg.out_channels, h, w), torch.float32, zero=True)
         ctx = TRef(P.ctx, B * 77, cfg.cross_attention_dim, name="ctx")
         if self.sweep:      # per-sample LoRA strengths of `fwd_on`: written by the caller, read by every `lora_rowscale` launch
-            P.strengths = self.strengths = self.buf("strengths", (B,), torch.float32)
+            # a `LoRAStack` of F files: fp32 [B][F], and ONE device copy of its column -> file table for every site
+            self.col_file = eng.stack_col_file()
+            files = () if self.col_file is None else (len(eng.network.file_ranks),)
+            P.strengths = self.strengths = self.buf("strengths", (B,) + files, torch.float32)
             self.strengths.fill_(1.0)
         # -- time embedding
         tsin = self.act("t_sin", B, ch[0])
@@ -1531,7 +1550,7 @@ class UNet2DConditionModel(nn.Module):
             eng.refresh_lora(1.0)
         token = (net._strengths_version, id(net))
         if getattr(plan, "strengths_src", None) != token:
-            plan.strengths.copy_(torch.tensor(list(vec) * (B // len(vec)), dtype=torch.float32))
+            plan.strengths.copy_(torch.tensor(list(vec) * (B // len(vec)), dtype=torch.float32))      # (a stack: [B][F])
             plan.strengths_src = token
         return plan
 

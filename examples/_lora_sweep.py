@@ -92,13 +92,16 @@ def load_network(unet, args, scales):
     return network
 
 
-def write_sheet(latents, vae_path, png_path, dev, use_graphs=False, cols=None):
+def write_sheet(latents, vae_path, png_path, dev, use_graphs=False, cols=None, on_pictures=None):
     """Decode every latent and save the pictures as one PNG: ``cols`` per row, left to right, rows top to bottom (None: one
-    row of width n * W)."""
+    row of width n * W).  ``on_pictures``: called with the uint8 [n][H][W][3] pictures before the sheet is assembled
+    (`--clip_score`)."""
     from leco_amd.vae import save_png
     vae = model_util.load_vae(vae_path).to(dev)
     vae.use_graphs = use_graphs
     img = vae.decode_to_uint8(latents.float())          # [n][H][W][3]
+    if on_pictures is not None:
+        on_pictures(img)
     cols = img.shape[0] if cols is None else cols
     rows = [torch.cat(list(img[i:i + cols]), dim=1) for i in range(0, img.shape[0], cols)]
     sheet = torch.cat(rows, dim=0).contiguous()

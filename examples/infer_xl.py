@@ -27,6 +27,10 @@ batch (`LoRANetwork.set_strengths`, bf16 only); `--image` becomes a contact shee
 `--lora` may be repeated: the files are stacked (`LoRANetwork.from_files`), `--lora_multipliers a,b` sets one fixed multiplier
 per file, and `--lora_scales`, given once per `--lora` in the same order, samples the cross product in one batched pass (first
 file slowest; the contact sheet has the last file's strengths left to right, the other combinations top to bottom).
+
+`--clip_score TEXT` (repeatable, needs `--image`) scores every decoded picture against TEXT with the native CLIP image tower
+(`--clip_model`: a local transformers CLIPModel folder, or `synthetic:vit_tiny` -- the default for `synthetic:*` models): one
+line per picture, with its strengths in a sweep, and the same table in `<image stem>.scores.json` (`_clip_score.py`).
 """
 import argparse
 import contextlib
@@ -39,6 +43,7 @@ from safetensors.torch import save_file
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path[:0] = [os.path.dirname(HERE), HERE]
 from leco_amd import model_util, train_util  # noqa: E402
+import _clip_score  # noqa: E402
 import _lora_sweep  # noqa: E402
 from _img2img import init_latents  # noqa: E402
 
@@ -66,8 +71,10 @@ def main(argv=None):
     ap.add_argument("--strength", type=float, default=0.6, help="img2img: 0 < S <= 1, the share of the schedule that is run")
     ap.add_argument("--native_text_encoder", action="store_true",
                     help="encode the prompts with the native CLIP text encoder (leco_amd.clip, bf16 only) instead of transformers")
+    _clip_score.add_arguments(ap)
     args = ap.parse_args(_lora_sweep.join_scales(argv))
     scales = _lora_sweep.parse_scales(ap, args)
+    _clip_score.check(ap, args)
     n = 1 if scales is None else len(scales)
     dev = torch.device(args.device)
     dtype = torch.bfloat16
@@ -108,20 +115,25 @@ def main(argv=None):
     save_file({"latents": latents.float().cpu().contiguous()}, args.out,
               {"prompt": args.prompt, "steps": str(args.steps), "guidance_scale": str(args.guidance_scale)})
     print(f"Done. latents {tuple(latents.shape)} -> {args.out}")
+    score = _clip_score.hook(args, scales, dev, use_graphs=unet.use_graphs)
     if args.image and scales is None:
-        write_image(latents, args.vae or args.model, args.image, dev, use_graphs=unet.use_graphs)
+        write_image(latents, args.vae or args.model, args.image, dev, use_graphs=unet.use_graphs, on_pictures=score)
     elif args.image:
-        _lora_sweep.write_sheet(latents, args.vae or args.model, args.image, dev, use_graphs=unet.use_graphs, cols=args.sheet_cols)
+        _lora_sweep.write_sheet(latents, args.vae or args.model, args.image, dev, use_graphs=unet.use_graphs, cols=args.sheet_cols,
+                                on_pictures=score)
     return latents
 
 
-def write_image(latents, vae_path, png_path, dev, use_graphs=False):
+def write_image(latents, vae_path, png_path, dev, use_graphs=False, on_pictures=None):
     """test/infer_xl.py:136-154: decode (the division by the scaling factor happens inside `decode_to_uint8`), denormalise,
-    round to 8 bits (the output convolution's epilogue) and save the first image."""
+    round to 8 bits (the output convolution's epilogue) and save the first image.  ``on_pictures``: called with the uint8
+    [n][H][W][3] pictures where the decoder left them (`--clip_score`)."""
     from leco_amd.vae import save_png
     vae = model_util.load_vae(vae_path).to(dev)
     vae.use_graphs = use_graphs
     img = vae.decode_to_uint8(latents.float())
+    if on_pictures is not None:
+        on_pictures(img)
     save_png(img[0], png_path)
     vae.release()
     print(f"image {img.shape[2]}x{img.shape[1]} -> {png_path}")

@@ -295,6 +295,39 @@ int leco_attention_causal_fwd(const void* q, int64_t ldq, int64_t bsq, const voi
  * the EOS row of each sample for the pooled output (last_hidden_state[arange(B), eos_pos]). */
 int leco_embed_rows(const void* table, int64_t ldt, int32_t rows, const int32_t* idx, const void* pos, int64_t ldp,
                     int32_t period, void* out, int64_t ldo, int32_t n, int32_t c, leco_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * CLIP image tower and CLIP score (leco_amd/clip_vision.py; csrc/vision.hip).
+ * ---------------------------------------------------------------------- */
+/* transformers' CLIPImageProcessor + the patch flattening in one pass: img uint8 NHWC [batch][h][w][3] (any h, w >= 1) ->
+ * out bf16 [batch * P][ldo], P = (image_size / patch_size)^2, row b * P + py * (image_size / patch_size) + px = patch
+ * (py, px) of picture b; column c * p * p + i * p + j = channel c, pixel (i, j) of the patch (the flattening of
+ * patch_embedding.weight[out][3][p][p]); columns [3 p p, Kp) with Kp = 3 p p rounded up to a multiple of 64 are written as
+ * zeros (leco_gemm needs k % 64 == 0); ldo >= Kp, ldo % 8 == 0.
+ * The picture is resized so that its shortest edge is image_size with PIL's antialiased bicubic filter, centre-cropped to
+ * image_size x image_size, scaled by 1/255 and normalised, value = (level / 255 - mean[c]) / std[c].  The filter is
+ * separable; the caller passes it as two DEVICE tap tables that hold only the output rows / columns that survive the crop:
+ *   row_tab int32 [image_size][2] = (first source row, tap count <= row_taps), row_w fp32 [image_size][row_taps],
+ *   col_tab / col_w / col_taps likewise for the columns (`clip_vision.resize_taps`: PIL's precompute_coeffs rule).
+ * Per output pixel: the column taps along every source row of its window (that sum clamped to [0, 255], PIL's 8-bit
+ * intermediate picture saturates), then the row taps over those sums (clamped to [0, 255] again).  All arithmetic from the
+ * source bytes to the one final bf16 rounding is fp32: PIL's two roundings to whole levels are not made.  A table entry
+ * that points outside the picture is clamped into it, never followed.  mean_std: DEVICE fp32 [6] = mean[3], std[3]. */
+int leco_clip_preprocess(const void* img, int32_t batch, int32_t h, int32_t w, const int32_t* row_tab, const float* row_w,
+                         int32_t row_taps, const int32_t* col_tab, const float* col_w, int32_t col_taps,
+                         const float* mean_std, int32_t image_size, int32_t patch_size, void* out, int64_t ldo,
+                         leco_stream_t stream);
+/* CLIPVisionEmbeddings after the patch GEMM: out[b][0][:] = cls[:] + pos[0][:], out[b][1 + t][:] = patches[b][t][:] +
+ * pos[1 + t][:]; patches bf16 [batch * tokens][ldp], cls bf16 [c], pos bf16 [tokens + 1][ldpos], out bf16
+ * [batch * (tokens + 1)][ldo].  c % 8 == 0, strides multiples of 8; the sum is formed in fp32 and rounded once. */
+int leco_vit_embed(const void* patches, int64_t ldp, const void* cls, const void* pos, int64_t ldpos, void* out, int64_t ldo,
+                   int32_t batch, int32_t tokens, int32_t c, leco_stream_t stream);
+/* out[b][t] = scale * <x_b, y_t> / (max(|x_b|, 1e-12) * max(|y_t|, 1e-12)): x bf16 [nb][ldx], y bf16 [nt][ldy], out fp32
+ * [nb][ldo]; d % 8 == 0, ldx / ldy multiples of 8; the three sums in fp32, one wave per pair.  scale = 1: the cosines (the
+ * CLIP score); scale = exp(logit_scale): transformers' logits_per_image.  An all-zero row gives 0. */
+int leco_cosine_scores(const void* x, int64_t ldx, const void* y, int64_t ldy, float* out, int64_t ldo, int32_t nb, int32_t nt,
+                       int32_t d, float scale, leco_stream_t stream);
+
 /* GEGLU (diffusers FeedForward ff.net.0): y[m][f] = u[m][f] * gelu_erf(u[m][F+f]) */
 int leco_geglu_fwd(const void* u, int64_t ldu, void* y, int64_t ldy, int32_t m, int32_t f,
                    leco_stream_t stream);

@@ -11,7 +11,9 @@
   ``leco_amd/ckpt_convert.py`` (architecture detected from tensor shapes, key map derived from the block
   structure; CLIP-L / OpenCLIP-H text towers rebuilt as ``transformers`` models);
 * ``native_text_encoder=True`` (opt-in) returns ``leco_amd.clip`` text encoders -- the same towers on the HIP kernels,
-  bf16 only -- instead of the ``transformers`` models; the tokenizers stay ``transformers``'.
+  bf16 only -- instead of the ``transformers`` models; the tokenizers stay ``transformers``';
+* ``load_clip_scorer`` (opt-in, the CLIP score of samples) reads a local transformers ``CLIPModel`` folder or builds
+  ``synthetic:vit_tiny`` / ``synthetic:vit_l`` into a `leco_amd.clip_vision.ClipScorer`.
 """
 from __future__ import annotations
 
@@ -349,6 +351,66 @@ def load_vae(path: str, precision: str = "bfloat16", scaling_factor: Optional[fl
         sd = cc.convert_ldm_vae(cc.read_checkpoint(p), encoder)
         return _load_state_into_vae(V.AutoencoderKL(cc.detect_vae_config(sd, scaling_factor), encoder=encoder), sd, p)
     raise FileNotFoundError(f"{p}: not a local diffusers folder, single-file checkpoint or synthetic:<sd15|sd21|sdxl|tiny|tiny_xl>")
+
+
+SYNTHETIC_CLIP_SCORER = ("vit_tiny", "vit_l")
+
+
+def load_clip_scorer(path: str, native_text_encoder: bool = False):
+    """A `leco_amd.clip_vision.ClipScorer` (native image tower + a text side + tokenizer) from
+
+    * a local transformers ``CLIPModel`` folder: ``config.json`` with ``vision_config`` / ``text_config``,
+      ``model.safetensors`` / ``pytorch_model.bin``, the tokenizer files.  The text side is transformers'
+      ``CLIPTextModelWithProjection``, or with ``native_text_encoder=True`` the native one (`leco_amd.clip`, bf16 only);
+    * ``synthetic:vit_tiny`` / ``synthetic:vit_l``: seeded random weights of that shape; the text side is a hash-noise
+      stand-in vector of ``projection_dim`` per prompt (as `SyntheticTextEncoder`), whatever ``native_text_encoder`` says.
+
+    Anything else is a FileNotFoundError: nothing is fetched.  A missing or unexpected key of a tower is a KeyError naming it."""
+    from . import clip as CL
+    from . import clip_vision as CV
+    if path.startswith("synthetic:"):
+        kind = path.split(":", 1)[1]
+        if kind not in SYNTHETIC_CLIP_SCORER:
+            raise FileNotFoundError(f"{path}: unknown synthetic CLIP model (synthetic:vit_tiny | synthetic:vit_l)")
+        cfg = CV.vit_tiny_config() if kind == "vit_tiny" else CV.vit_l_14_config()
+        vision = CV.init_synthetic_clip_vision_(CV.CLIPVisionModelWithProjection(cfg)).to(torch.bfloat16)
+        return CV.ClipScorer(vision, CV.SyntheticTextEmbedder(cfg.projection_dim), CV.SyntheticTokenizer())
+    if not (os.path.isdir(path) and os.path.isfile(os.path.join(path, "config.json"))):
+        raise FileNotFoundError(f"{path}: not a local transformers CLIPModel folder (config.json, weights, tokenizer files) and "
+                                f"not synthetic:vit_tiny | synthetic:vit_l; nothing is fetched")
+    with open(os.path.join(path, "config.json")) as f:
+        cfg = json.load(f)
+    if "vision_config" not in cfg or "text_config" not in cfg:
+        raise FileNotFoundError(f"{path}/config.json: no vision_config / text_config (not a CLIPModel folder)")
+    from transformers import CLIPTokenizer
+    tokenizer = CLIPTokenizer.from_pretrained(path)
+    sd = _read_state_folder(path)
+    vision = CV.CLIPVisionModelWithProjection(CV.CLIPVisionConfig.from_json(os.path.join(path, "config.json")))
+    vision.load_state_dict(CV.vision_state_dict(sd))
+    tc = {k: v for k, v in cfg["text_config"].items() if v is not None}
+    if cfg.get("projection_dim"):
+        tc["projection_dim"] = cfg["projection_dim"]
+    tc.setdefault("eos_token_id", tokenizer.eos_token_id)
+    tc.setdefault("bos_token_id", tokenizer.bos_token_id)
+    tsd = CV.text_state_dict(sd)
+    if native_text_encoder:
+        text = CL.CLIPTextModelWithProjection(CL.CLIPTextConfig.from_dict(tc))
+        text.load_state_dict(tsd)
+        text = text.to(torch.bfloat16)
+    else:
+        from transformers import CLIPTextConfig, CLIPTextModelWithProjection
+        known = set(CL.CLIPTextConfig.__dataclass_fields__)
+        text = CLIPTextModelWithProjection(CLIPTextConfig(**{k: v for k, v in tc.items() if k in known})).eval()
+        want = text.state_dict()
+        if not any(k.startswith("text_model.") for k in want):              # transformers >= 5 dropped the prefix
+            tsd = {k[len("text_model."):] if k.startswith("text_model.") else k: v for k, v in tsd.items()}
+        lacking = [k for k in want if k not in tsd and not k.endswith("position_ids")]
+        if lacking:
+            raise KeyError(f"{path}: the text tower lacks {lacking[0]!r}")
+        text.load_state_dict({k: v for k, v in tsd.items() if k in want}, strict=False)
+        text.requires_grad_(False)
+    scale = float(sd["logit_scale"]) if "logit_scale" in sd else math.log(1 / 0.07)
+    return CV.ClipScorer(vision.to(torch.bfloat16), text, tokenizer, logit_scale=scale)
 
 
 def load_models(pretrained_model_name_or_path: str, scheduler_name: str, v2: bool = False, v_pred: bool = False,

@@ -31,6 +31,9 @@ _SIGS = {
                            _i32, _i32, _i32, _i32, _i32, _f32, _vp],
     "leco_attention_causal_fwd": [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _f32, _vp],
     "leco_embed_rows": [_vp, _i64, _i32, _vp, _vp, _i64, _i32, _vp, _i64, _i32, _i32, _vp],
+    "leco_clip_preprocess": [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _i64, _vp],
+    "leco_vit_embed": [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp],
+    "leco_cosine_scores": [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _f32, _vp],
     "leco_gemm_ex": [C.POINTER(GemmArgs), _i32, _i32, _vp, _i64, _vp],
     "leco_geglu_fwd": [_vp, _i64, _vp, _i64, _i32, _i32, _vp],
     "leco_geglu_bwd": [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp],
@@ -269,6 +272,28 @@ def embed_rows_checked(table: torch.Tensor, ids: torch.Tensor, pos: Optional[tor
     idx = check_row_ids(ids, rows).to(table.device)
     return embed_rows(table, table.stride(0), rows, idx, pos, 0 if pos is None else pos.stride(0), period, out, out.stride(0),
                       idx.numel(), c)
+
+
+def clip_preprocess(img, batch, h, w, row_tab, row_w, row_taps, col_tab, col_w, col_taps, mean_std, image_size, patch_size,
+                    out, ldo, keep=None) -> Op:
+    """uint8 NHWC ``img`` [batch][h][w][3] -> bf16 patch rows ``out`` [batch * P][ldo]: antialiased bicubic resize of the
+    shortest edge to ``image_size``, centre crop, 1/255, mean / std, patch flattening, zero padding up to a multiple of 64
+    columns.  The tap tables (`clip_vision.resize_taps`) and ``mean_std`` (fp32 [6]) are DEVICE tensors, see
+    include/leco_hip.h."""
+    return Op("leco_clip_preprocess", (ptr(img), batch, h, w, ptr(row_tab), ptr(row_w), row_taps, ptr(col_tab), ptr(col_w), col_taps,
+                                       ptr(mean_std), image_size, patch_size, ptr(out), ldo),
+              keep=(img, row_tab, row_w, col_tab, col_w, mean_std, out, keep))
+
+
+def vit_embed(patches, ldp, cls, pos, ldpos, out, ldo, batch, tokens, c, keep=None) -> Op:
+    """out[b][0] = cls + pos[0], out[b][1 + t] = patches[b][t] + pos[1 + t] on bf16 rows (fp32 sum, one rounding)."""
+    return Op("leco_vit_embed", (ptr(patches), ldp, ptr(cls), ptr(pos), ldpos, ptr(out), ldo, batch, tokens, c),
+              keep=(patches, cls, pos, out, keep))
+
+
+def cosine_scores(x, ldx, y, ldy, out, ldo, nb, nt, d, scale: float = 1.0, keep=None) -> Op:
+    """out[b][t] = scale * cos(x[b], y[t]): bf16 ``x`` [nb][d], ``y`` [nt][d] -> fp32 ``out`` [nb][nt]."""
+    return Op("leco_cosine_scores", (ptr(x), ldx, ptr(y), ldy, ptr(out), ldo, nb, nt, d, float(scale)), keep=(x, y, out, keep))
 
 
 def geglu_fwd(u, ldu, y, ldy, m, f) -> Op:

@@ -31,6 +31,10 @@ file slowest; the contact sheet has the last file's strengths left to right, the
 `--clip_score TEXT` (repeatable, needs `--image`) scores every decoded picture against TEXT with the native CLIP image tower
 (`--clip_model`: a local transformers CLIPModel folder, or `synthetic:vit_tiny` -- the default for `synthetic:*` models): one
 line per picture, with its strengths in a sweep, and the same table in `<image stem>.scores.json` (`_clip_score.py`).
+
+`--attn_map WORD` (repeatable, needs `--image`) draws where in the picture WORD of the prompt acts: the cross-attention heat of
+its tokens over every decoded picture (`<image stem>.attn.png`, the layout of `--image` once per word, top to bottom) and the
+mean heat per cell in `<image stem>.attn.json`; `#3` / `#3-5` name raw token positions (`_attn_map.py`).
 """
 import argparse
 import contextlib
@@ -43,6 +47,7 @@ from safetensors.torch import save_file
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path[:0] = [os.path.dirname(HERE), HERE]
 from leco_amd import model_util, train_util  # noqa: E402
+import _attn_map  # noqa: E402
 import _clip_score  # noqa: E402
 import _lora_sweep  # noqa: E402
 from _img2img import init_latents  # noqa: E402
@@ -72,9 +77,11 @@ def main(argv=None):
     ap.add_argument("--native_text_encoder", action="store_true",
                     help="encode the prompts with the native CLIP text encoder (leco_amd.clip, bf16 only) instead of transformers")
     _clip_score.add_arguments(ap)
+    _attn_map.add_arguments(ap)
     args = ap.parse_args(_lora_sweep.join_scales(argv))
     scales = _lora_sweep.parse_scales(ap, args)
     _clip_score.check(ap, args)
+    _attn_map.check(ap, args)
     n = 1 if scales is None else len(scales)
     dev = torch.device(args.device)
     dtype = torch.bfloat16
@@ -97,6 +104,7 @@ def main(argv=None):
     text_embeds = train_util.concat_embeddings(neg, pos, n)
     add_text_embeds = train_util.concat_embeddings(neg_pooled, pos_pooled, n)
     add_time_ids = train_util.concat_embeddings(add_time_ids, add_time_ids, n)
+    amap = _attn_map.start(args, unet, tokenizers[0], args.prompt)
     sched.set_timesteps(args.steps, device=dev)
     torch.manual_seed(args.seed)
     t_start = 0
@@ -116,6 +124,7 @@ def main(argv=None):
               {"prompt": args.prompt, "steps": str(args.steps), "guidance_scale": str(args.guidance_scale)})
     print(f"Done. latents {tuple(latents.shape)} -> {args.out}")
     score = _clip_score.hook(args, scales, dev, use_graphs=unet.use_graphs)
+    score = _attn_map.hook(args, scales, unet, amap, cols=args.sheet_cols, also=score)
     if args.image and scales is None:
         write_image(latents, args.vae or args.model, args.image, dev, use_graphs=unet.use_graphs, on_pictures=score)
     elif args.image:

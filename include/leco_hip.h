@@ -328,6 +328,44 @@ int leco_vit_embed(const void* patches, int64_t ldp, const void* cls, const void
 int leco_cosine_scores(const void* x, int64_t ldx, const void* y, int64_t ldy, float* out, int64_t ldo, int32_t nb, int32_t nt,
                        int32_t d, float scale, leco_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Cross-attention token heatmaps (leco_amd/attn_maps.py, `Engine.plan(attn_maps=M)`; csrc/attn_maps.hip).
+ * ---------------------------------------------------------------------- */
+/* DAAM-style token maps from the Q and K operands of one cross-attention:
+ *   maps[b][m][i] += step_w[0] / heads * sum_h sum_j tok_w[m][j] * softmax_j(scale * <q_bhi, k_bhj>)
+ * q, k: bf16 in the operand convention of leco_attention_fwd (token stride ld*, batch stride bs*, head h in columns
+ * [h*d, (h+1)*d)), 16-byte aligned, strides multiples of 8; k may be a column view of the [B*skv][k|v] buffer `attn2.kv`
+ * writes.  tok_w: DEVICE fp32 [n_maps][skv], 1 <= n_maps <= 8 (a word of several tokens = a row with several ones).
+ * step_w: DEVICE fp32 [1], read when the launch RUNS (a captured graph weights or mutes a step without a new capture).
+ * maps: fp32 [batch][n_maps][sq], accumulated in place.  The kernel forms its own row maximum and row sum (all skv <= 128
+ * keys of a row are one tile; no lse buffer is read); Q K^T on the bf16 MFMAs with fp32 accumulation, everything from the
+ * scores to the store in fp32 (no P is rounded to bf16).  Every (b, m, i) has exactly one owner and the heads are summed in a
+ * fixed order: no atomics, two runs give equal bits.  Key columns past skv are masked by selection (whatever lies behind
+ * the last key row, a NaN included, never reaches the output); rows past sq are neither read nor written.
+ * head_dim in {40, 64, 80, 160} (the cross-attention widths of SD1.x / SD2.x / SDXL) or 32 (the synthetic tiny models),
+ * 1 <= skv <= 128, any sq >= 1; anything else is -EINVAL with leco_last_error set, and nothing is launched. */
+int leco_xattn_token_maps(const void* q, int64_t ldq, int64_t bsq, const void* k, int64_t ldk, int64_t bsk,
+                          const float* tok_w, int32_t n_maps, const float* step_w, float* maps, int32_t batch,
+                          int32_t heads, int32_t sq, int32_t skv, int32_t head_dim, float scale, leco_stream_t stream);
+/* heat[p][y][x] = sum_l weight_l * bilinear(map_l[p] -> ht x wt)(y, x), p < planes (= samples x words): `layers` is a DEVICE
+ * table of n_layers entries, map_l fp32 [planes][h_l][w_l], any h_l, w_l, ht, wt >= 1.  The bilinear rule is
+ * torch.nn.functional.interpolate(mode="bilinear", align_corners=False): source index max((in / out) (dst + 0.5) - 0.5, 0),
+ * the upper tap clamped to the last row / column; fp32 throughout, layers added in table order. */
+typedef struct leco_attn_map_layer {
+    const float* map;
+    int32_t h, w;
+    float weight;
+} leco_attn_map_layer;
+int leco_attn_maps_merge(const leco_attn_map_layer* layers, int32_t n_layers, float* heat, int32_t planes, int32_t ht,
+                         int32_t wt, leco_stream_t stream);
+/* Heat map `map_index` of every sample blended over its picture: heat fp32 [batch][n_maps][ht][wt], rmax DEVICE fp32
+ * [batch * n_maps] (the reciprocal of the value that maps to full heat, per map), pic / out uint8 [batch][ht][wt][3], lut
+ * DEVICE uint8 [256][3] (the colour table), 0 <= alpha <= 1.  Per pixel, in fp32:
+ *   v = min(max(heat * rmax, 0), 1)  (a NaN gives 0),  c = lut[floor(255 v + 0.5)],
+ *   out = floor(pic * (1 - alpha v) + c * (alpha v) + 0.5)     -- round half up, the sum clamped to [0, 255] first. */
+int leco_heat_overlay(const float* heat, const float* rmax, const void* pic, const void* lut, void* out, int32_t batch,
+                      int32_t n_maps, int32_t map_index, int32_t ht, int32_t wt, float alpha, leco_stream_t stream);
+
 /* GEGLU (diffusers FeedForward ff.net.0): y[m][f] = u[m][f] * gelu_erf(u[m][F+f]) */
 int leco_geglu_fwd(const void* u, int64_t ldu, void* y, int64_t ldy, int32_t m, int32_t f,
                    leco_stream_t stream);

@@ -34,6 +34,9 @@ _SIGS = {
     "leco_clip_preprocess": [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _i64, _vp],
     "leco_vit_embed": [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp],
     "leco_cosine_scores": [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _f32, _vp],
+    "leco_xattn_token_maps": [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp],
+    "leco_attn_maps_merge": [_vp, _i32, _vp, _i32, _i32, _i32, _vp],
+    "leco_heat_overlay": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp],
     "leco_gemm_ex": [C.POINTER(GemmArgs), _i32, _i32, _vp, _i64, _vp],
     "leco_geglu_fwd": [_vp, _i64, _vp, _i64, _i32, _i32, _vp],
     "leco_geglu_bwd": [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp],
@@ -294,6 +297,40 @@ def vit_embed(patches, ldp, cls, pos, ldpos, out, ldo, batch, tokens, c, keep=No
 def cosine_scores(x, ldx, y, ldy, out, ldo, nb, nt, d, scale: float = 1.0, keep=None) -> Op:
     """out[b][t] = scale * cos(x[b], y[t]): bf16 ``x`` [nb][d], ``y`` [nt][d] -> fp32 ``out`` [nb][nt]."""
     return Op("leco_cosine_scores", (ptr(x), ldx, ptr(y), ldy, ptr(out), ldo, nb, nt, d, float(scale)), keep=(x, y, out, keep))
+
+
+TOKEN_MAPS_MAX, TOKEN_MAPS_MAX_KEYS = 8, 128
+TOKEN_MAPS_HEAD_DIMS = (32, 40, 64, 80, 160)
+
+
+def xattn_token_maps(q, ldq, bsq, k, ldk, bsk, tok_w, n_maps, step_w, maps, batch, heads, sq, skv, d, scale, keep=None) -> Op:
+    """maps[b][m][i] += step_w / heads * sum_h sum_j tok_w[m][j] softmax_j(scale <q_bhi, k_bhj>): ``q`` / ``k`` are raw device
+    addresses of bf16 operands as `attention_fwd` takes them, ``tok_w`` fp32 [n_maps][skv], ``step_w`` fp32 [1] and ``maps``
+    fp32 [batch][n_maps][sq] are DEVICE tensors (include/leco_hip.h).  bf16 compute mode only."""
+    if _f32_active:
+        raise NotImplementedError("xattn_token_maps (attention heatmaps) is implemented for the bf16 compute mode only")
+    return Op("leco_xattn_token_maps", (ptr(q), ldq, bsq, ptr(k), ldk, bsk, ptr(tok_w), n_maps, ptr(step_w), ptr(maps), batch, heads,
+                                        sq, skv, d, float(scale)), keep=(tok_w, step_w, maps, keep))
+
+
+def attn_map_layers(layers: Sequence[tuple], device) -> torch.Tensor:
+    """The DEVICE table of `attn_maps_merge` (`leco_attn_map_layer`: pointer, h, w, weight) from (map tensor or address, h, w,
+    weight) tuples, as raw bytes."""
+    import struct
+    raw = b"".join(struct.pack("<Qiif4x", ptr(m), int(h), int(w), float(wgt)) for m, h, w, wgt in layers)      # 24 bytes: 8-aligned
+    return torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(device)
+
+
+def attn_maps_merge(table: torch.Tensor, n_layers: int, heat: torch.Tensor, planes: int, ht: int, wt: int, keep=None) -> Op:
+    """heat[p] = sum_l weight_l * bilinear(map_l[p] -> ht x wt) (torch's align_corners=False rule); ``table``: `attn_map_layers`."""
+    return Op("leco_attn_maps_merge", (ptr(table), n_layers, ptr(heat), planes, ht, wt), keep=(table, heat, keep))
+
+
+def heat_overlay(heat, rmax, pic, lut, out, batch, n_maps, map_index, ht, wt, alpha) -> Op:
+    """out = the uint8 pictures ``pic`` [batch][ht][wt][3] with heat map ``map_index`` of ``heat`` [batch][n_maps][ht][wt] blended
+    over them through the colour table ``lut`` (uint8 [256][3]); ``rmax``: fp32 [batch * n_maps] reciprocal full-heat values."""
+    return Op("leco_heat_overlay", (ptr(heat), ptr(rmax), ptr(pic), ptr(lut), ptr(out), batch, n_maps, map_index, ht, wt, float(alpha)),
+              keep=(heat, rmax, pic, lut, out))
 
 
 def geglu_fwd(u, ldu, y, ldy, m, f) -> Op:

@@ -544,7 +544,7 @@ class Engine:
     SWEEP_TAG = "sweep"      # Engine.plan(..., strengths=True) keys its plans with this tag
 
     def plan(self, B: int, h: int, w: int, need_bwd: bool = True, ws_slot: int = 0, share: int = 1, tag: Optional[str] = None,
-             strengths: bool = False) -> Plan:
+             strengths: bool = False, attn_maps: int = 0, cond_rows: Optional[int] = None) -> Plan:
         """``need_bwd=False`` builds a forward-only plan (no gradient buffers): used for the batched
         LoRA-off passes, which never run a backward.  ``ws_slot`` > 0 gives the plan's split-K launches a workspace of
         their own (the only mutable buffer plans share), so that its lists may run CONCURRENTLY with another plan's on a
@@ -554,7 +554,25 @@ class Engine:
         the prompt embeddings is then computed once per distinct sample (`PlanBuilder.shared_prefix`).  ``strengths=True``
         (forward-only, bf16 only): the SWEEP variant -- its ``fwd_on`` list applies every LoRA site at a strength of its
         own per sample, read from the plan buffer ``strengths`` (fp32 [B]; [B][F] for a `LoRAStack` of F files) when the list runs
-        (`PlanBuilder.sweep`)."""
+        (`PlanBuilder.sweep`).  ``attn_maps=M`` (forward-only, bf16 only; combines with ``strengths``): the MAPS variant -- every
+        block takes the per-op route, and behind each cross-attention's ``to_q`` / ``kv`` a `leco_xattn_token_maps` launch adds
+        the M token maps of the last ``cond_rows`` samples (default: B / 2, the conditional half of a CFG-doubled batch
+        [uncond; cond]) to a per-layer plan buffer (`PlanBuilder.token_maps`)."""
+        if attn_maps:
+            if self.f32:
+                raise NotImplementedError("attention maps: compute precision 'float32' is not implemented (bfloat16 only; "
+                                          "`train.precision: float32` does not extend to the maps plans)")
+            if need_bwd or share > 1:
+                raise ValueError("attention maps exist on forward-only plans without a shared prefix")
+            if not 1 <= attn_maps <= ops.TOKEN_MAPS_MAX:
+                raise ValueError(f"attention maps: {attn_maps} maps requested, 1..{ops.TOKEN_MAPS_MAX} are supported")
+            if cond_rows is None:
+                if B % 2:
+                    raise ValueError(f"attention maps: a batch of {B} is not CFG-doubled [uncond; cond]; pass cond_rows")
+                cond_rows = B // 2
+            if not 1 <= cond_rows <= B:
+                raise ValueError(f"attention maps: cond_rows={cond_rows} outside 1..{B}")
+            tag = (tag + "." if tag else "") + f"maps{attn_maps}x{cond_rows}"
         if strengths:
             if self.f32:
                 raise NotImplementedError("per-sample LoRA strengths: compute precision 'float32' is not implemented (bfloat16 "
@@ -573,7 +591,8 @@ class Engine:
         if key not in self.plans:
             with ops.f32_mode(self.f32):
                 self.plans[key] = PlanBuilder(self, B, h, w, need_bwd, ws=self.workspace_slot(ws_slot), share=share,
-                                              **({"sweep": True} if strengths else {})).build()
+                                              **({"sweep": True} if strengths else {}),
+                                              **({"attn_maps": attn_maps, "cond_rows": cond_rows} if attn_maps else {})).build()
                 self.plans[key].key = key
         return self.plans[key]
 
@@ -606,8 +625,12 @@ class Engine:
 
 class PlanBuilder:
     def __init__(self, eng: Engine, B: int, h: int, w: int, need_bwd: bool = True, ws: Optional[torch.Tensor] = None,
-                 share: int = 1, sweep: bool = False):
+                 share: int = 1, sweep: bool = False, attn_maps: int = 0, cond_rows: int = 0):
         self.eng, self.cfg, self.dev = eng, eng.cfg, eng.device
+        # MAPS variant (forward-only, bf16): no stripe kernels, so `q2` and `kv` of every cross-attention exist in memory, and a
+        # `leco_xattn_token_maps` launch behind them accumulates the token maps of the last `cond_rows` samples (`token_maps`)
+        self.attn_maps, self.cond_rows = attn_maps, cond_rows
+        assert not attn_maps or (not need_bwd and share == 1 and not eng.f32 and 1 <= cond_rows <= B)
         self.share = share
         # SWEEP variant (forward-only, bf16): every LoRA site of `fwd_on` takes the unfused route -- the down GEMM writes the
         # low-rank image T, `lora_rowscale` scales the rows of sample b by strengths[b], the main launch consumes T through
@@ -1128,7 +1151,7 @@ class PlanBuilder:
         """The row-stripe fused kernels (csrc/stripe.hip) cover this block: forward-only bf16 plan, a supported shape, and
         LoRA operands (if any) in the 32-column packed form.  LECO_STRIPE=0 keeps the per-op launches (A/B measurements)."""
         import os
-        if self.need_bwd or self.eng.f32 or os.environ.get("LECO_STRIPE", "1") == "0":
+        if self.need_bwd or self.eng.f32 or self.attn_maps or os.environ.get("LECO_STRIPE", "1") == "0":
             return False
         if not ops.xblock_supported(Cc, heads, skv, hw):
             return False
@@ -1231,6 +1254,8 @@ class PlanBuilder:
         kv = self.gemm_fwd(S[bname + ".attn2.kv"], ctx, bname + ".kv", rows=ctx.rows)
         for op in self.f_on[n_on:] + self.f_off[n_off:]:
             op.tag = "ctx"
+        if self.attn_maps:
+            self.token_maps(bname, q2, kv, heads, hw, ctx.rows // self.B)
         a2 = self.attention(q2, kv, heads, hw, ctx.rows // self.B, bname + ".a2")
         h2 = self.gemm_fwd(S[bname + ".attn2.to_out.0"], a2, bname + ".h2", rows=rows, residual=h1)
         ff1 = S[bname + ".ff.net.0.proj"]
@@ -1254,6 +1279,21 @@ class PlanBuilder:
                 u.gparts.append(du)
             self.tape.append(bwd)
         return self.gemm_fwd(S[bname + ".ff.net.2"], gg, bname + ".h3", rows=rows, residual=h2), False
+
+    def token_maps(self, bname: str, q2: TRef, kv: TRef, heads: int, hw: int, skv: int) -> None:
+        """MAPS variant: the token maps of one cross-attention, from its `to_q` output and the k half of its `kv` buffer --
+        maps[b][m][i] += step_w / heads * sum_h sum_j tok_w[m][j] softmax_j(q k^T / sqrt(d)) over the LAST `cond_rows` samples
+        of the batch, addressed by pointer offset.  The launch only reads activations; it sits in both forward lists, so a
+        captured graph carries it.  The layer buffer (fp32 [cond_rows][M][hw]) is zeroed by the plan's `maps_reset` list."""
+        Cc, Bc, M = q2.cols, self.cond_rows, self.attn_maps
+        d = Cc // heads
+        skip = self.B - Bc
+        buf = self.buf(bname + ".token_maps", (Bc, M, hw), torch.float32, zero=True)
+        self.plan.attn_layers.append((bname, buf, hw))
+        self.both(ops.xattn_token_maps(q2.ptr + skip * hw * q2.ld * self.eng.esz, q2.ld, hw * q2.ld,
+                                       kv.ptr + skip * skv * kv.ld * self.eng.esz, kv.ld, skv * kv.ld,
+                                       self.plan.tok_w, M, self.plan.step_w, buf, Bc, heads, hw, skv, d, d ** -0.5, keep=(q2, kv)))
+        self.plan.lists["maps_reset"].append(ops.memset(buf))
 
     def block_head_fused(self, tname: str, bname: str, x: TRef, hw: int) -> Tuple[TRef, TRef]:
         """GroupNorm (from the statistics the producer of x left, else the per-op GroupNorm first) + proj_in + norm1 + q|k|v of
@@ -1325,6 +1365,13 @@ class PlanBuilder:
             files = () if self.col_file is None else (len(eng.network.file_ranks),)
             P.strengths = self.strengths = self.buf("strengths", (B,) + files, torch.float32)
             self.strengths.fill_(1.0)
+        if self.attn_maps:      # token weights and the step weight: written by the caller, read by every `token_maps` launch
+            P.tok_w = self.buf("tok_w", (self.attn_maps, 77), torch.float32, zero=True)
+            P.step_w = self.buf("step_w", (1,), torch.float32)
+            P.step_w.fill_(1.0)
+            P.attn_layers = []      # (block name, fp32 [cond_rows][M][hw] buffer, hw) in forward order
+            P.attn_hw = (h, w)
+            P.lists["maps_reset"] = []
         # -- time embedding
         tsin = self.act("t_sin", B, ch[0])
         self.both(ops.timestep_embedding(P.t_table, P.t_idx, 0, B, ch[0], tsin.t))
@@ -1487,6 +1534,7 @@ class UNet2DConditionModel(nn.Module):
         self.conv_out = nn.Conv2d(ch[0], cfg.out_channels, 3, 1, 1)
         self._engine: Optional[Engine] = None
         self.use_graphs = False
+        self._attn_tok_w = None      # (token weights, cond_rows, identity token) while `set_attention_maps` is on
 
     # ---- reference call sites that are no-ops here (train_lora.py:68) ------------------------------
     def enable_xformers_memory_efficient_attention(self, *a, **k):
@@ -1532,7 +1580,7 @@ class UNet2DConditionModel(nn.Module):
             eng.refresh_lora(net.multiplier)
         return eng.plan(B, h, w, tag=tag)
 
-    def prepare_sweep(self, sample_shape) -> Plan:
+    def prepare_sweep(self, sample_shape, attn_maps: int = 0, cond_rows: Optional[int] = None) -> Plan:
         """The SWEEP plan of this shape (`Engine.plan(strengths=True)`) with ``network.strengths`` in its strength buffer: row b
         of the batch runs at strengths[b % len(strengths)] -- `predict_noise` doubles the batch as [uncond...; cond...], so the
         vector is tiled.  The packed `up` images keep multiplier = 1; a change of strengths is one small host-to-device copy, no
@@ -1544,7 +1592,7 @@ class UNet2DConditionModel(nn.Module):
         if B % len(vec):
             raise ValueError(f"per-sample LoRA strengths: the UNet batch of {B} is not a whole multiple of the {len(vec)} strengths "
                              f"{tuple(vec)} (set_strengths)")
-        plan = eng.plan(B, h, w, need_bwd=False, strengths=True)     # (raises in the fp32 compute mode, before any re-pack)
+        plan = eng.plan(B, h, w, need_bwd=False, strengths=True, attn_maps=attn_maps, cond_rows=cond_rows)     # (raises in the fp32 compute mode, before any re-pack)
         if net.needs_repack() or eng._pack_scale != 1.0:
             net.sync_shadow()
             eng.refresh_lora(1.0)
@@ -1552,6 +1600,77 @@ class UNet2DConditionModel(nn.Module):
         if getattr(plan, "strengths_src", None) != token:
             plan.strengths.copy_(torch.tensor(list(vec) * (B // len(vec)), dtype=torch.float32))      # (a stack: [B][F])
             plan.strengths_src = token
+        return plan
+
+    # ---- attention heatmaps ---------------------------------------------------------------------------
+    def set_attention_maps(self, tok_w: Optional[torch.Tensor], cond_rows: Optional[int] = None) -> None:
+        """Collect cross-attention token maps from now on: ``tok_w`` fp32 [M][77] (`attn_maps.token_weights`: one row per word,
+        ones at its token positions), M <= 8.  While it is set, `forward` runs the MAPS plan of its shape
+        (`Engine.plan(attn_maps=M)`; the sweep variant of it when strengths are set) and every cross-attention adds the maps
+        of the last ``cond_rows`` samples of the batch (default: half of it, the conditional half of `predict_noise`'s
+        [uncond; cond]) to its layer buffer -- forward-only, bf16 only.  ``None`` restores the normal plans."""
+        if tok_w is None:
+            self._attn_tok_w = None
+            return
+        tok_w = torch.as_tensor(tok_w, dtype=torch.float32)
+        if tok_w.ndim != 2 or tok_w.shape[1] != 77 or not 1 <= tok_w.shape[0] <= ops.TOKEN_MAPS_MAX:
+            raise ValueError(f"set_attention_maps: token weights must be [M <= {ops.TOKEN_MAPS_MAX}][77], got {tuple(tok_w.shape)}")
+        self._attn_tok_w = (tok_w.detach().clone(), cond_rows, object())
+
+    def _maps_plans(self) -> List[Plan]:
+        return [] if self._engine is None else [p for p in self._engine.plans.values() if hasattr(p, "attn_layers")]
+
+    def reset_attention_maps(self) -> None:
+        """Zero the layer maps of every maps plan (a new sampling run)."""
+        for p in self._maps_plans():
+            ops.run_plan(p.lists["maps_reset"])
+
+    def set_attention_step_weight(self, w: float) -> None:
+        """Weight of the following passes in the maps (0 mutes them); read on the device, no new graph capture."""
+        for p in self._maps_plans():
+            p.step_w.fill_(float(w))
+
+    def attention_maps(self, size: Tuple[int, int], layer_weights: Optional[Sequence[float]] = None) -> torch.Tensor:
+        """The maps collected by the last maps pass, merged: fp32 [cond_rows][M][H][W] = sum over the cross-attention layers of
+        weight_l * bilinear(layer map -> ``size``) (`leco_attn_maps_merge`).  ``layer_weights``: one per layer in forward
+        order; default 1 / layers (the plain average)."""
+        plan = self.__dict__.get("_attn_plan")
+        if plan is None or plan.key not in self.engine().plans:
+            raise RuntimeError("attention_maps: no pass has run with set_attention_maps")
+        layers = plan.attn_layers
+        wts = [1.0 / len(layers)] * len(layers) if layer_weights is None else [float(v) for v in layer_weights]
+        if len(wts) != len(layers):
+            raise ValueError(f"attention_maps: {len(wts)} layer weights for {len(layers)} cross-attention layers")
+        h, w = plan.attn_hw
+        table = []
+        for (name, buf, hw), wt in zip(layers, wts):
+            f = int(round(math.sqrt(h * w / hw)))      # this level's down-sampling factor
+            lh, lw = -(-h // f), -(-w // f)
+            assert lh * lw == hw, (name, h, w, hw)
+            table.append((buf, lh, lw, wt))
+        Bc, M = layers[0][1].shape[:2]
+        heat = torch.empty((Bc, M, int(size[0]), int(size[1])), dtype=torch.float32, device=self.device)
+        ops.attn_maps_merge(ops.attn_map_layers(table, self.device), len(table), heat, Bc * M, int(size[0]), int(size[1])).run()
+        return heat
+
+    def prepare_maps(self, sample_shape, lora_on: bool, sweep: bool) -> Plan:
+        """The MAPS plan of this shape with the token weights of `set_attention_maps` in its buffer."""
+        tok_w, cond_rows, token = self._attn_tok_w
+        M = tok_w.shape[0]
+        if sweep:
+            plan = self.prepare_sweep(sample_shape, attn_maps=M, cond_rows=cond_rows)
+        else:
+            B, _, h, w = sample_shape
+            eng = self.engine()
+            plan = eng.plan(B, h, w, need_bwd=False, attn_maps=M, cond_rows=cond_rows)      # (raises in the fp32 mode, before any re-pack)
+            net = eng.network
+            if net is not None and lora_on and (net.needs_repack() or eng._pack_scale != net.multiplier):
+                net.sync_shadow()
+                eng.refresh_lora(net.multiplier)
+        if getattr(plan, "tok_w_src", None) is not token:
+            plan.tok_w.copy_(tok_w)
+            plan.tok_w_src = token
+        self._attn_plan = plan
         return plan
 
     def lora_active(self) -> bool:
@@ -1587,7 +1706,11 @@ class UNet2DConditionModel(nn.Module):
         eng = self.engine()
         lora_on = self.lora_active()
         sweep = lora_on and getattr(eng.network, "strengths", None) is not None
-        plan = self.prepare_sweep(sample.shape) if sweep else self.prepare(sample.shape, lora_on)
+        maps = self.__dict__.get("_attn_tok_w") is not None
+        if maps:
+            plan = self.prepare_maps(sample.shape, lora_on, sweep)
+        else:
+            plan = self.prepare_sweep(sample.shape) if sweep else self.prepare(sample.shape, lora_on)
         plan.x_in.copy_(sample)
         plan.set_ctx(encoder_hidden_states)
         t = torch.as_tensor(timestep)
@@ -1599,6 +1722,9 @@ class UNet2DConditionModel(nn.Module):
         net = eng.network
         if sweep:      # forward-only: no autograd node
             self._run(plan, "fwd_on")
+            return UNetOutput(plan.pred.to(sample.dtype))
+        if maps:       # forward-only as well
+            self._run(plan, "fwd_on" if lora_on else "fwd_off")
             return UNetOutput(plan.pred.to(sample.dtype))
         if lora_on and torch.is_grad_enabled() and net is not None and net.slab.requires_grad:
             return UNetOutput(_UNetFn.apply(net.slab, self, plan, sample.dtype))

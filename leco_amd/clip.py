@@ -7,7 +7,7 @@ The module tree only HOLDS weights under the transformers parameter names (``tex
 layer_norm2, mlp.fc1, mlp.fc2}``, ``text_model.final_layer_norm``, ``text_projection``), so an HF state dict -- or the
 output of ``ckpt_convert.convert_ldm_clip`` / ``convert_open_clip`` -- loads with ``load_state_dict`` as is.  A call runs
 a forward-only launch plan built from ``ops.*`` per (batch, sequence length): bf16 activations, fp32 accumulation;
-replayed from a hipGraph when ``use_graphs`` is set.
+replayed from a hipGraph when ``use_graphs`` is set.  The N layers are the stack of ``encoder.py``, shared with the image tower.
 
     token + position embedding                           leco_embed_rows
     N x  layer_norm1                                     leco_layernorm_fwd
@@ -27,18 +27,15 @@ from __future__ import annotations
 
 import json
 from dataclasses import dataclass, fields
-from typing import Dict, List, Optional, Tuple
+from typing import List, Optional
 
 import torch
 from torch import nn
 
 from . import graphs, ops
-from .hip import ACT_GELU, ACT_NONE, ACT_QUICK_GELU, gemm_args
+from .encoder import ACTS, LN_EPS, EncoderEngine, EncoderPlan, f32, init_synthetic_encoder_, pack_encoder_layers, wb
 
-bf16 = torch.bfloat16
-LN_EPS = 1e-5
 HEAD_DIM = 64                    # what leco_attention_causal_fwd is built for: every CLIP tower SD uses
-ACTS = {"quick_gelu": ACT_QUICK_GELU, "gelu": ACT_GELU}
 
 
 @dataclass
@@ -163,108 +160,66 @@ class CLIPTextOutput:
 
 
 # ---- launch plan ---------------------------------------------------------------------------------------------------------------
-class CLIPPlan:
+class CLIPPlan(EncoderPlan):
     def __init__(self):
-        self.ops: List[ops.Op] = []
-        self.names: List[str] = []               # one label per launch (tools/bench_clip.py --per-op)
-        self.graph = None
+        super().__init__()
         self.ids: torch.Tensor = None            # int32 [B * S]: token ids
         self.eos_idx: torch.Tensor = None        # int32 [B]: row b * S + (EOS position of sample b) of the hidden states
         self.hidden: List[torch.Tensor] = []     # bf16 [B * S][C]: the embeddings, then every layer's output
         self.last: torch.Tensor = None           # bf16 [B * S][C]: final_layer_norm of the last layer's output
         self.pooled: torch.Tensor = None         # bf16 [B][C]
         self.text_embeds: Optional[torch.Tensor] = None     # bf16 [B][projection_dim]
-        self.keep: list = []
 
 
-class CLIPEngine(graphs.PlanEngine):
+class CLIPEngine(EncoderEngine):
     """Packed device operands of one text encoder and its launch plans, keyed by (batch, sequence length)."""
 
     def __init__(self, model: "CLIPTextModel", device: torch.device):
-        super().__init__(device)
-        self.cfg = model.cfg
-        self.workspace = torch.empty(2 * 1024 * 1024, dtype=torch.float32, device=device)      # split-K partial slabs
-        f32 = lambda t: t.detach().float().to(device).contiguous()      # noqa: E731
-        wb = lambda t: t.detach().to(device, bf16).contiguous()          # noqa: E731
         tm = model.text_model
-        self.tok, self.pos = wb(tm.embeddings.token_embedding.weight), wb(tm.embeddings.position_embedding.weight)
-        self.gemm_w: Dict[str, Tuple[torch.Tensor, Optional[torch.Tensor]]] = {}
-        self.norm_p: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
-        for i, l in enumerate(tm.encoder.layers):
-            a = l.self_attn
-            self.gemm_w[f"{i}.qkv"] = (wb(torch.cat([a.q_proj.weight, a.k_proj.weight, a.v_proj.weight], 0)),
-                                       f32(torch.cat([a.q_proj.bias, a.k_proj.bias, a.v_proj.bias], 0)))
-            self.gemm_w[f"{i}.out"] = (wb(a.out_proj.weight), f32(a.out_proj.bias))
-            self.gemm_w[f"{i}.fc1"] = (wb(l.mlp.fc1.weight), f32(l.mlp.fc1.bias))
-            self.gemm_w[f"{i}.fc2"] = (wb(l.mlp.fc2.weight), f32(l.mlp.fc2.bias))
-            self.norm_p[f"{i}.ln1"] = (f32(l.layer_norm1.weight), f32(l.layer_norm1.bias))
-            self.norm_p[f"{i}.ln2"] = (f32(l.layer_norm2.weight), f32(l.layer_norm2.bias))
-        self.norm_p["final"] = (f32(tm.final_layer_norm.weight), f32(tm.final_layer_norm.bias))
+        super().__init__(model.cfg, device)
+        self.tok, self.pos = wb(tm.embeddings.token_embedding.weight, device), wb(tm.embeddings.position_embedding.weight, device)
+        self.gemm_w, self.norm_p = pack_encoder_layers(tm.encoder.layers, device)
+        self.norm_p["final"] = (f32(tm.final_layer_norm.weight, device), f32(tm.final_layer_norm.bias, device))
         proj = getattr(model, "text_projection", None)
-        self.proj_w = None if proj is None else wb(proj.weight)
+        self.proj_w = None if proj is None else wb(proj.weight, device)
 
     # -- plan construction ----------------------------------------------------------------------------------------------------
     def _build(self, B: int, S: int) -> CLIPPlan:
         cfg, dev = self.cfg, self.device
-        Cw, Fw, H, M = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads, B * S
+        Cw, H, M = cfg.hidden_size, cfg.num_attention_heads, B * S
         p = CLIPPlan()
-        buf = lambda rows, cols: torch.zeros(rows, cols, dtype=bf16, device=dev)      # noqa: E731
         p.ids = torch.zeros(M, dtype=torch.int32, device=dev)
         p.eos_idx = torch.zeros(B, dtype=torch.int32, device=dev)
-        p.hidden = [buf(M, Cw) for _ in range(cfg.num_hidden_layers + 1)]
-        n, qkv, att, h1, u = buf(M, Cw), buf(M, 3 * Cw), buf(M, Cw), buf(M, Cw), buf(M, Fw)
-        mean, rstd = torch.zeros(M, device=dev), torch.zeros(M, device=dev)
-        p.keep = [n, qkv, att, h1, u, mean, rstd]
+        p.hidden = [self.buf(M, Cw) for _ in range(cfg.num_hidden_layers + 1)]      # `hidden_states` wants every layer's output
+        self.scratch(p, M)
 
-        def add(name, op):
-            p.ops.append(op)
-            p.names.append(name)
-
-        def ln(name, x, y):
-            g, b = self.norm_p[name]
-            add("layernorm", ops.layernorm_fwd(x, Cw, g, b, cfg.layer_norm_eps, M, Cw, y, Cw, mean, rstd))
-
-        def gemm(label, name, x, y, k, act=ACT_NONE, residual=None):
-            w, bias = self.gemm_w[name]
-            g = gemm_args(x, w, y, m=M, n=w.shape[0], k=k, bias=bias, residual=residual, act=act)
-            add(label, ops.gemm(g, keep=(w, bias, x, y, residual), ws=self.workspace))
-
-        add("embed", ops.embed_rows(self.tok, Cw, cfg.vocab_size, p.ids, self.pos, Cw, S, p.hidden[0], Cw, M, Cw))
-        for i in range(cfg.num_hidden_layers):
-            x, y = p.hidden[i], p.hidden[i + 1]
-            ln(f"{i}.ln1", x, n)
-            gemm("qkv", f"{i}.qkv", n, qkv, Cw)
+        def attention(qkv, att):
             q0, ld = qkv.data_ptr(), 3 * Cw
-            add("attention", ops.attention_causal_fwd(q0, ld, S * ld, q0 + 2 * Cw, ld, S * ld, q0 + 4 * Cw, ld, S * ld, att.data_ptr(),
-                                                      Cw, S * Cw, B, H, S, HEAD_DIM, HEAD_DIM ** -0.5, keep=(qkv, att)))
-            gemm("out_proj", f"{i}.out", att, h1, Cw, residual=x)
-            ln(f"{i}.ln2", h1, n)
-            gemm("fc1", f"{i}.fc1", n, u, Cw, act=ACTS[cfg.hidden_act])
-            gemm("fc2", f"{i}.fc2", u, y, Fw, residual=h1)
-        p.last = buf(M, Cw)
-        ln("final", p.hidden[-1], p.last)
-        p.pooled = buf(B, Cw)
-        add("eos_gather", ops.embed_rows(p.last, Cw, M, p.eos_idx, None, 0, 1, p.pooled, Cw, B, Cw))
+            return ops.attention_causal_fwd(q0, ld, S * ld, q0 + 2 * Cw, ld, S * ld, q0 + 4 * Cw, ld, S * ld, att.data_ptr(),
+                                            Cw, S * Cw, B, H, S, HEAD_DIM, HEAD_DIM ** -0.5, keep=(qkv, att))
+
+        p.add("embed", ops.embed_rows(self.tok, Cw, cfg.vocab_size, p.ids, self.pos, Cw, S, p.hidden[0], Cw, M, Cw))
+        for i in range(cfg.num_hidden_layers):
+            self.layer(p, i, p.hidden[i], p.hidden[i + 1], M, attention)
+        p.last = self.buf(M, Cw)
+        self.ln(p, "final", p.hidden[-1], p.last, M)
+        p.pooled = self.buf(B, Cw)
+        p.add("eos_gather", ops.embed_rows(p.last, Cw, M, p.eos_idx, None, 0, 1, p.pooled, Cw, B, Cw))
         if self.proj_w is not None:
-            P = self.proj_w.shape[0]
-            p.text_embeds = buf(B, P)
-            g = gemm_args(p.pooled, self.proj_w, p.text_embeds, m=B, n=P, k=Cw)
-            add("projection", ops.gemm(g, keep=(self.proj_w, p.pooled, p.text_embeds), ws=self.workspace))
+            p.text_embeds = self.buf(B, self.proj_w.shape[0])
+            self.gemm(p, "projection", self.proj_w, None, p.pooled, p.text_embeds, B, Cw)
         return p
 
     def plan(self, B: int, S: int) -> CLIPPlan:
-        key = (B, S)
-        p = self.plans.get(key)
-        if p is None:
-            p = self.plans[key] = self._build(B, S)
-        return p
+        return self.cached((B, S), lambda: self._build(B, S))
 
 
 class CLIPTextModel(graphs.ForwardOnlyModel):
-    """transformers' ``CLIPTextModel``, forward only.  Compute is bf16 with fp32 accumulation whatever dtype the parameters
-    are held in; outputs come back in that dtype."""
+    """transformers' ``CLIPTextModel``, forward only."""
     _first = "last_hidden_state"
     engine_type = CLIPEngine
+    label = "CLIP text encoder"
+    bf16_only = "bfloat16 only; `train.precision: float32` does not extend to the native text encoder"
 
     def __init__(self, cfg: Optional[CLIPTextConfig] = None):
         super().__init__(use_graphs=True)
@@ -272,9 +227,7 @@ class CLIPTextModel(graphs.ForwardOnlyModel):
         self.text_model = CLIPTextTransformer(self.cfg)
         self.requires_grad_(False)
 
-    @property
-    def config(self) -> CLIPTextConfig:
-        return self.cfg
+    load_state_dict = graphs.ForwardOnlyModel.load_strict      # an HF state dict as is; a wrong key is a KeyError
 
     @property
     def device(self):
@@ -283,24 +236,6 @@ class CLIPTextModel(graphs.ForwardOnlyModel):
     @property
     def dtype(self):
         return self.text_model.final_layer_norm.weight.dtype
-
-    def load_state_dict(self, state_dict, strict: bool = True, **kw):
-        """A missing or unexpected key is a KeyError naming it (``position_ids``, a buffer of older checkpoints, is ignored)."""
-        sd = {k: v for k, v in state_dict.items() if not k.endswith("position_ids")}
-        missing, unexpected = super().load_state_dict(sd, strict=False, **kw)
-        if strict and missing:
-            raise KeyError(f"CLIP text encoder: the state dict lacks {missing[0]!r}"
-                           + (f" (and {len(missing) - 1} more)" if len(missing) > 1 else ""))
-        if strict and unexpected:
-            raise KeyError(f"CLIP text encoder: unexpected key {unexpected[0]!r}"
-                           + (f" (and {len(unexpected) - 1} more)" if len(unexpected) > 1 else ""))
-        return missing, unexpected
-
-    def set_precision(self, precision) -> "CLIPTextModel":
-        if precision not in ("bfloat16", "bf16", torch.bfloat16):
-            raise NotImplementedError(f"CLIP text encoder: compute precision {precision!r} is not implemented (bfloat16 only; "
-                                      "`train.precision: float32` does not extend to the native text encoder)")
-        return self
 
     def eos_positions(self, ids: torch.Tensor) -> torch.Tensor:
         """transformers' pooling rule: the first position equal to ``eos_token_id``, or argmax of the ids for the legacy
@@ -328,8 +263,7 @@ class CLIPTextModel(graphs.ForwardOnlyModel):
     def forward(self, input_ids, output_hidden_states: bool = False, **kw) -> CLIPTextOutput:
         plan = self._encode(input_ids)
         B, S = torch.as_tensor(input_ids).shape
-        dt = self.dtype
-        out = lambda t, *shape: t.view(*shape).to(dt, copy=True)      # noqa: E731  (the plan's buffers are reused by the next call)
+        out = self.copy_out
         hs = tuple(out(h, B, S, -1) for h in plan.hidden) if output_hidden_states else None
         te = None if plan.text_embeds is None else out(plan.text_embeds, B, -1)
         return CLIPTextOutput(self._first, out(plan.last, B, S, -1), out(plan.pooled, B, -1), te, hs)
@@ -346,18 +280,5 @@ class CLIPTextModelWithProjection(CLIPTextModel):
 
 
 def init_synthetic_clip_(model: CLIPTextModel, seed: int = 2468) -> CLIPTextModel:
-    """Seeded random weights of the scale of a trained tower (embeddings ~ N(0, 0.02), Linear U(+-1/sqrt(fan_in)),
-    LayerNorm gamma near 1): measurement tools and tests, no checkpoint exists on the build boxes."""
-    g = torch.Generator().manual_seed(seed)
-    with torch.no_grad():
-        for name, p in model.named_parameters():
-            if "embedding" in name:
-                p.copy_(torch.randn(p.shape, generator=g) * 0.02)
-            elif p.ndim == 2:
-                p.copy_((torch.rand(p.shape, generator=g) * 2 - 1) / p.shape[1] ** 0.5)
-            elif "norm" in name and name.endswith("weight"):
-                p.copy_(1.0 + 0.1 * torch.randn(p.shape, generator=g))
-            else:
-                p.copy_(0.02 * torch.randn(p.shape, generator=g))
-    model.release()
-    return model
+    """Seeded stand-in weights (`encoder.init_synthetic_encoder_`)."""
+    return init_synthetic_encoder_(model, seed)

@@ -7,7 +7,8 @@ patch_embedding.weight, position_embedding.weight}``, ``vision_model.pre_layrnor
 ``vision_model.post_layernorm``, ``visual_projection.weight``), so an HF state dict -- or that part of a full ``CLIPModel``
 file, `vision_state_dict` -- loads with ``load_state_dict`` as is.  A call runs a forward-only launch plan per batch size
 (and, for raw pixels, per picture size): bf16 activations, fp32 accumulation; replayed from a hipGraph when ``use_graphs``
-is set.  T = (image_size / patch_size)^2 patches, T + 1 tokens:
+is set.  The N layers are the stack of ``encoder.py``, shared with the text encoder.  T = (image_size / patch_size)^2 patches,
+T + 1 tokens:
 
     [raw pixels only] resize + crop + normalise + patchify   leco_clip_preprocess
     patch embedding (no bias), K = 3 p p padded to 64        leco_gemm
@@ -39,16 +40,15 @@ import hashlib
 import json
 import math
 from dataclasses import dataclass, fields
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 from torch import nn
 
 from . import graphs, ops
-from .clip import ACTS, LN_EPS, CLIPEncoder
-from .hip import ACT_NONE, gemm_args
+from .clip import CLIPEncoder
+from .encoder import ACTS, LN_EPS, EncoderEngine, EncoderPlan, bf16, f32, init_synthetic_encoder_, pack_encoder_layers, wb
 
-bf16 = torch.bfloat16
 HEAD_DIMS = (64, 80)             # the widths of leco_attention_fwd a CLIP image tower uses
 OPENAI_CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
 OPENAI_CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
@@ -222,47 +222,30 @@ class CLIPVisionOutput:
 
 
 # ---- launch plan ---------------------------------------------------------------------------------------------------------------
-class VisionPlan:
+class VisionPlan(EncoderPlan):
     def __init__(self):
-        self.ops: List[ops.Op] = []
-        self.names: List[str] = []               # one label per launch (tools/bench_clip_vision.py --per-op)
-        self.graph = None
+        super().__init__()
         self.img: Optional[torch.Tensor] = None  # uint8 [B][H][W][3]: raw pixels (plans of `encode_images` only)
         self.patches: torch.Tensor = None        # bf16 [B * T][Kp]: the patch GEMM's operand
         self.last: torch.Tensor = None           # bf16 [B * (T + 1)][C]: the encoder's output
         self.pooled: torch.Tensor = None         # bf16 [B][C]
         self.image_embeds: torch.Tensor = None   # bf16 [B][projection_dim]
-        self.keep: list = []
 
 
-class VisionEngine(graphs.PlanEngine):
+class VisionEngine(EncoderEngine):
     """Packed device operands of one image tower and its launch plans, keyed by (batch,) for preprocessed pixels and by
     (batch, height, width) for raw ones."""
 
     def __init__(self, model: "CLIPVisionModelWithProjection", device: torch.device):
-        super().__init__(device)
-        cfg = self.cfg = model.cfg
-        self.workspace = torch.empty(2 * 1024 * 1024, dtype=torch.float32, device=device)      # split-K partial slabs
-        f32 = lambda t: t.detach().float().to(device).contiguous()      # noqa: E731
-        wb = lambda t: t.detach().to(device, bf16).contiguous()          # noqa: E731
-        vm = model.vision_model
+        cfg, vm = model.cfg, model.vision_model
+        super().__init__(cfg, device)
         pw = vm.embeddings.patch_embedding.weight.detach().reshape(cfg.hidden_size, -1)
-        self.patch_w = wb(torch.nn.functional.pad(pw, (0, cfg.patch_k - pw.shape[1])))
-        self.cls, self.pos = wb(vm.embeddings.class_embedding), wb(vm.embeddings.position_embedding.weight)
-        self.gemm_w: Dict[str, Tuple[torch.Tensor, Optional[torch.Tensor]]] = {}
-        self.norm_p: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
-        for i, l in enumerate(vm.encoder.layers):
-            a = l.self_attn
-            self.gemm_w[f"{i}.qkv"] = (wb(torch.cat([a.q_proj.weight, a.k_proj.weight, a.v_proj.weight], 0)),
-                                       f32(torch.cat([a.q_proj.bias, a.k_proj.bias, a.v_proj.bias], 0)))
-            self.gemm_w[f"{i}.out"] = (wb(a.out_proj.weight), f32(a.out_proj.bias))
-            self.gemm_w[f"{i}.fc1"] = (wb(l.mlp.fc1.weight), f32(l.mlp.fc1.bias))
-            self.gemm_w[f"{i}.fc2"] = (wb(l.mlp.fc2.weight), f32(l.mlp.fc2.bias))
-            self.norm_p[f"{i}.ln1"] = (f32(l.layer_norm1.weight), f32(l.layer_norm1.bias))
-            self.norm_p[f"{i}.ln2"] = (f32(l.layer_norm2.weight), f32(l.layer_norm2.bias))
-        self.norm_p["pre"] = (f32(vm.pre_layrnorm.weight), f32(vm.pre_layrnorm.bias))
-        self.norm_p["post"] = (f32(vm.post_layernorm.weight), f32(vm.post_layernorm.bias))
-        self.proj_w = wb(model.visual_projection.weight)
+        self.patch_w = wb(torch.nn.functional.pad(pw, (0, cfg.patch_k - pw.shape[1])), device)
+        self.cls, self.pos = wb(vm.embeddings.class_embedding, device), wb(vm.embeddings.position_embedding.weight, device)
+        self.gemm_w, self.norm_p = pack_encoder_layers(vm.encoder.layers, device)
+        self.norm_p["pre"] = (f32(vm.pre_layrnorm.weight, device), f32(vm.pre_layrnorm.bias, device))
+        self.norm_p["post"] = (f32(vm.post_layernorm.weight, device), f32(vm.post_layernorm.bias, device))
+        self.proj_w = wb(model.visual_projection.weight, device)
         self.mean_std = torch.tensor(cfg.image_mean + cfg.image_std, dtype=torch.float32, device=device)
         self.tables: Dict[Tuple[int, int], tuple] = {}
 
@@ -281,74 +264,53 @@ class VisionEngine(graphs.PlanEngine):
     # -- plan construction ----------------------------------------------------------------------------------------------------
     def _build(self, B: int, hw: Optional[Tuple[int, int]]) -> VisionPlan:
         cfg, dev = self.cfg, self.device
-        Cw, Fw, H, D = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads, cfg.head_dim
+        Cw, H, D = cfg.hidden_size, cfg.num_attention_heads, cfg.head_dim
         T, Kp = cfg.num_patches, cfg.patch_k
         S, M = T + 1, B * (T + 1)
-        p = VisionPlan()
-        buf = lambda rows, cols: torch.zeros(rows, cols, dtype=bf16, device=dev)      # noqa: E731
+        p, buf = VisionPlan(), self.buf
         p.patches = buf(B * T, Kp)
         pe, x0 = buf(B * T, Cw), buf(M, Cw)
         xa, xb = buf(M, Cw), buf(M, Cw)              # the residual stream ping-pongs between two buffers
-        n, qkv, att, h1, u = buf(M, Cw), buf(M, 3 * Cw), buf(M, Cw), buf(M, Cw), buf(M, Fw)
-        mean, rstd = torch.zeros(M, device=dev), torch.zeros(M, device=dev)
+        self.scratch(p, M)
         lse = torch.zeros(B * H * S, device=dev)
         cls_idx = (torch.arange(B, dtype=torch.int32) * S).to(dev)
         cls_row = buf(B, Cw)
-        p.keep = [pe, x0, xa, xb, n, qkv, att, h1, u, mean, rstd, lse, cls_idx, cls_row]
+        p.keep = [pe, x0, xa, xb, lse, cls_idx, cls_row]
 
-        def add(name, op):
-            p.ops.append(op)
-            p.names.append(name)
-
-        def ln(name, x, y, rows=M):
-            g, b = self.norm_p[name]
-            add("layernorm", ops.layernorm_fwd(x, Cw, g, b, cfg.layer_norm_eps, rows, Cw, y, Cw, mean, rstd))
-
-        def gemm(label, w, bias, x, y, m, k, act=ACT_NONE, residual=None):
-            g = gemm_args(x, w, y, m=m, n=w.shape[0], k=k, bias=bias, residual=residual, act=act)
-            add(label, ops.gemm(g, keep=(w, bias, x, y, residual), ws=self.workspace))
+        def attention(qkv, att):
+            q0, ld = qkv.data_ptr(), 3 * Cw
+            return ops.attention_fwd(q0, ld, S * ld, q0 + 2 * Cw, ld, S * ld, q0 + 4 * Cw, ld, S * ld, att.data_ptr(),
+                                     Cw, S * Cw, lse, B, H, S, S, D, D ** -0.5)
 
         if hw is not None:
             h, w = hw
             p.img = torch.zeros(B, h, w, 3, dtype=torch.uint8, device=dev)
             rt, rw, rk, ct, cw, ck = self._tables(h, w)
-            add("preprocess", ops.clip_preprocess(p.img, B, h, w, rt, rw, rk, ct, cw, ck, self.mean_std, cfg.image_size,
-                                                  cfg.patch_size, p.patches, Kp))
-        gemm("patch_embed", self.patch_w, None, p.patches, pe, B * T, Kp)
-        add("embed", ops.vit_embed(pe, Cw, self.cls, self.pos, Cw, x0, Cw, B, T, Cw))
-        ln("pre", x0, xa)
+            p.add("preprocess", ops.clip_preprocess(p.img, B, h, w, rt, rw, rk, ct, cw, ck, self.mean_std, cfg.image_size,
+                                                    cfg.patch_size, p.patches, Kp))
+        self.gemm(p, "patch_embed", self.patch_w, None, p.patches, pe, B * T, Kp)
+        p.add("embed", ops.vit_embed(pe, Cw, self.cls, self.pos, Cw, x0, Cw, B, T, Cw))
+        self.ln(p, "pre", x0, xa, M)
         x, y = xa, xb
         for i in range(cfg.num_hidden_layers):
-            ln(f"{i}.ln1", x, n)
-            gemm("qkv", *self.gemm_w[f"{i}.qkv"], n, qkv, M, Cw)
-            q0, ld = qkv.data_ptr(), 3 * Cw
-            add("attention", ops.attention_fwd(q0, ld, S * ld, q0 + 2 * Cw, ld, S * ld, q0 + 4 * Cw, ld, S * ld, att.data_ptr(),
-                                               Cw, S * Cw, lse, B, H, S, S, D, D ** -0.5))
-            gemm("out_proj", *self.gemm_w[f"{i}.out"], att, h1, M, Cw, residual=x)
-            ln(f"{i}.ln2", h1, n)
-            gemm("fc1", *self.gemm_w[f"{i}.fc1"], n, u, M, Cw, act=ACTS[cfg.hidden_act])
-            gemm("fc2", *self.gemm_w[f"{i}.fc2"], u, y, M, Fw, residual=h1)
+            self.layer(p, i, x, y, M, attention)
             x, y = y, x
         p.last = x
-        add("cls_gather", ops.embed_rows(p.last, Cw, M, cls_idx, None, 0, 1, cls_row, Cw, B, Cw))
+        p.add("cls_gather", ops.embed_rows(p.last, Cw, M, cls_idx, None, 0, 1, cls_row, Cw, B, Cw))
         p.pooled = buf(B, Cw)
-        ln("post", cls_row, p.pooled, rows=B)
+        self.ln(p, "post", cls_row, p.pooled, B)
         p.image_embeds = buf(B, cfg.projection_dim)
-        gemm("projection", self.proj_w, None, p.pooled, p.image_embeds, B, Cw)
+        self.gemm(p, "projection", self.proj_w, None, p.pooled, p.image_embeds, B, Cw)
         return p
 
     def plan(self, B: int, hw: Optional[Tuple[int, int]] = None) -> VisionPlan:
-        key = (B,) if hw is None else (B, *hw)
-        p = self.plans.get(key)
-        if p is None:
-            p = self.plans[key] = self._build(B, hw)
-        return p
+        return self.cached((B,) if hw is None else (B, *hw), lambda: self._build(B, hw))
 
 
 class CLIPVisionModelWithProjection(graphs.ForwardOnlyModel):
-    """transformers' ``CLIPVisionModelWithProjection``, forward only.  Compute is bf16 with fp32 accumulation whatever dtype
-    the parameters are held in; outputs come back in that dtype."""
+    """transformers' ``CLIPVisionModelWithProjection``, forward only."""
     engine_type = VisionEngine
+    label = "CLIP image tower"
 
     def __init__(self, cfg: Optional[CLIPVisionConfig] = None):
         super().__init__(use_graphs=True)
@@ -356,10 +318,6 @@ class CLIPVisionModelWithProjection(graphs.ForwardOnlyModel):
         self.vision_model = CLIPVisionTransformer(self.cfg)
         self.visual_projection = nn.Linear(self.cfg.hidden_size, self.cfg.projection_dim, bias=False)
         self.requires_grad_(False)
-
-    @property
-    def config(self) -> CLIPVisionConfig:
-        return self.cfg
 
     @property
     def device(self):
@@ -370,27 +328,14 @@ class CLIPVisionModelWithProjection(graphs.ForwardOnlyModel):
         return self.visual_projection.weight.dtype
 
     def load_state_dict(self, state_dict, strict: bool = True, **kw):
-        """A missing or unexpected key is a KeyError naming it (``position_ids``, a buffer of older checkpoints, is ignored)."""
-        sd = {k: v for k, v in state_dict.items() if not k.endswith("position_ids")}
+        """An HF state dict as is; a wrong key is a KeyError."""
+        sd = state_dict
         if sd and not any(k.startswith("vision_model.") for k in sd):      # a transformers that saves without the prefix
             sd = {(k if k.startswith("visual_projection.") else "vision_model." + k): v for k, v in sd.items()}
-        missing, unexpected = super().load_state_dict(sd, strict=False, **kw)
-        if strict and missing:
-            raise KeyError(f"CLIP image tower: the state dict lacks {missing[0]!r}"
-                           + (f" (and {len(missing) - 1} more)" if len(missing) > 1 else ""))
-        if strict and unexpected:
-            raise KeyError(f"CLIP image tower: unexpected key {unexpected[0]!r}"
-                           + (f" (and {len(unexpected) - 1} more)" if len(unexpected) > 1 else ""))
-        return missing, unexpected
-
-    def set_precision(self, precision) -> "CLIPVisionModelWithProjection":
-        if precision not in ("bfloat16", "bf16", torch.bfloat16):
-            raise NotImplementedError(f"CLIP image tower: compute precision {precision!r} is not implemented (bfloat16 only)")
-        return self
+        return self.load_strict(sd, strict, **kw)
 
     def _output(self, plan: VisionPlan, B: int) -> CLIPVisionOutput:
-        dt = self.dtype
-        out = lambda t, *shape: t.view(*shape).to(dt, copy=True)      # noqa: E731  (the plan's buffers are reused by the next call)
+        out = self.copy_out
         return CLIPVisionOutput(out(plan.image_embeds, B, -1), out(plan.last, B, self.cfg.num_patches + 1, -1),
                                 out(plan.pooled, B, -1))
 
@@ -427,21 +372,8 @@ class CLIPVisionModelWithProjection(graphs.ForwardOnlyModel):
 
 
 def init_synthetic_clip_vision_(model: CLIPVisionModelWithProjection, seed: int = 1357) -> CLIPVisionModelWithProjection:
-    """Seeded random weights of the scale of a trained tower (embeddings ~ N(0, 0.02), Linear / patch convolution
-    U(+-1/sqrt(fan_in)), LayerNorm gamma near 1): measurement tools and tests."""
-    g = torch.Generator().manual_seed(seed)
-    with torch.no_grad():
-        for name, p in model.named_parameters():
-            if "class_embedding" in name or "position_embedding" in name:
-                p.copy_(torch.randn(p.shape, generator=g) * 0.02)
-            elif p.ndim >= 2:
-                p.copy_((torch.rand(p.shape, generator=g) * 2 - 1) / p[0].numel() ** 0.5)
-            elif "norm" in name and name.endswith("weight"):
-                p.copy_(1.0 + 0.1 * torch.randn(p.shape, generator=g))
-            else:
-                p.copy_(0.02 * torch.randn(p.shape, generator=g))
-    model.release()
-    return model
+    """Seeded stand-in weights (`encoder.init_synthetic_encoder_`)."""
+    return init_synthetic_encoder_(model, seed)
 
 
 def vision_state_dict(sd: dict) -> dict:

@@ -8,7 +8,7 @@ of its own (``model._capture_stream``, created on first use); nothing here owns 
 from __future__ import annotations
 
 import ctypes as C
-from typing import Iterable, MutableMapping, Optional, Sequence
+from typing import Callable, Iterable, MutableMapping, Optional, Sequence
 
 import torch
 from torch import nn
@@ -100,13 +100,20 @@ def replay_us(oplist: Sequence[ops.Op], reps: int = 20, warm: int = 3) -> float:
     return e0.elapsed_time(e1) / reps * 1e3
 
 
-# ---- the forward-only models (VAE, CLIP text encoder) --------------------------------------------------------------------------
+# ---- the forward-only models (VAE; the CLIP text encoder and image tower, one encoder stack: encoder.py) ------------------------
 class PlanEngine:
     """Packed device operands of one model and its launch plans by shape; a plan keeps its graph in ``plan.graph``."""
 
     def __init__(self, device: torch.device):
         self.device = device
         self.plans: dict = {}
+
+    def cached(self, key, build: Callable):
+        """``plans[key]``, made by ``build()`` on first use."""
+        p = self.plans.get(key)
+        if p is None:
+            p = self.plans[key] = build()
+        return p
 
     def release(self) -> None:
         destroy(self.device, [p.graph for p in self.plans.values()])
@@ -116,13 +123,40 @@ class PlanEngine:
 class ForwardOnlyModel(nn.Module):
     """A module tree that only holds weights and runs launch plans from an engine (``engine_type(model, device)``) built on
     first use.  The packed operands follow the parameters: anything that may change them -- ``.to()`` / ``.half()`` / ...
-    (``_apply``), ``load_state_dict`` -- drops the engine with its plans and graphs, and the next call rebuilds it."""
+    (``_apply``), ``load_state_dict`` -- drops the engine with its plans and graphs, and the next call rebuilds it.  Compute is
+    bf16 with fp32 accumulation whatever dtype the parameters are held in; outputs come back in that dtype.  A subclass keeps its
+    configuration in ``self.cfg``."""
     engine_type: type = None
+    label: str = None                        # "CLIP text encoder": what this model's error messages start with
+    bf16_only: str = "bfloat16 only"         # `set_precision`'s refusal, in the parentheses
 
     def __init__(self, use_graphs: bool):
         super().__init__()
         self.use_graphs = use_graphs
         self._engine: Optional[PlanEngine] = None
+
+    @property
+    def config(self):
+        return self.cfg
+
+    def set_precision(self, precision):
+        if precision not in ("bfloat16", "bf16", torch.bfloat16):
+            raise NotImplementedError(f"{self.label}: compute precision {precision!r} is not implemented ({self.bf16_only})")
+        return self
+
+    def load_strict(self, state_dict, strict: bool = True, **kw):
+        """A ``load_state_dict`` for the subclass that wants one: a missing or unexpected key is a KeyError naming it
+        (``position_ids``, a buffer of older checkpoints, is ignored)."""
+        sd = {k: v for k, v in state_dict.items() if not k.endswith("position_ids")}
+        missing, unexpected = ForwardOnlyModel.load_state_dict(self, sd, strict=False, **kw)
+        for what, keys in (("the state dict lacks", missing), ("unexpected key", unexpected)):
+            if strict and keys:
+                raise KeyError(f"{self.label}: {what} {keys[0]!r}" + (f" (and {len(keys) - 1} more)" if len(keys) > 1 else ""))
+        return missing, unexpected
+
+    def copy_out(self, t: torch.Tensor, *shape) -> torch.Tensor:
+        """A plan buffer as an output of this model's dtype; a copy, the next call reuses the plan's buffers."""
+        return t.view(*shape).to(self.dtype, copy=True)
 
     def engine(self):
         if self._engine is None or self._engine.device != self.device:

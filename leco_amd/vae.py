@@ -445,18 +445,10 @@ class VAEEngine(graphs.PlanEngine):
         """Keyed beside the decoder's plans; (H, W) is the image size."""
         if H % 8 or W % 8 or H <= 0 or W <= 0:
             raise ValueError(f"VAE encode: image height and width must be multiples of 8, got {H} x {W}")
-        key = ("encode", B, H, W, bool(u8), out)
-        p = self.plans.get(key)
-        if p is None:
-            p = self.plans[key] = _Builder(self, B, H, W).build_encoder(bool(u8), out)
-        return p
+        return self.cached(("encode", B, H, W, bool(u8), out), lambda: _Builder(self, B, H, W).build_encoder(bool(u8), out))
 
     def plan(self, B: int, h: int, w: int) -> VAEPlan:
-        key = (B, h, w)
-        p = self.plans.get(key)
-        if p is None:
-            p = self.plans[key] = _Builder(self, B, h, w).build()
-        return p
+        return self.cached((B, h, w), lambda: _Builder(self, B, h, w).build())
 
 
 class AutoencoderKL(graphs.ForwardOnlyModel):
@@ -465,6 +457,8 @@ class AutoencoderKL(graphs.ForwardOnlyModel):
     the sampler's latents as they are and divides by ``config.scaling_factor`` itself; `encode` follows diffusers (no
     scaling factor), `encode_to_latents` returns scaled latents."""
     engine_type = VAEEngine
+    label = "VAE decoder"
+    bf16_only = "bfloat16 only; `train.precision: float32` does not extend to the decoder"
 
     def __init__(self, cfg: Optional[VAEConfig] = None, encoder: bool = False):
         super().__init__(use_graphs=False)
@@ -482,19 +476,8 @@ class AutoencoderKL(graphs.ForwardOnlyModel):
         self.requires_grad_(False)
 
     @property
-    def config(self) -> VAEConfig:
-        return self.cfg
-
-    @property
     def device(self):
         return self.post_quant_conv.weight.device
-
-    def set_precision(self, precision) -> "AutoencoderKL":
-        """The decoder computes in bf16 with fp32 accumulation whatever dtype its parameters are held in."""
-        if precision not in ("bfloat16", "bf16", torch.bfloat16):
-            raise NotImplementedError(f"VAE decoder: compute precision {precision!r} is not implemented (bfloat16 only; "
-                                      "`train.precision: float32` does not extend to the decoder)")
-        return self
 
     def _decode(self, latents: torch.Tensor) -> VAEPlan:
         if latents.ndim != 4 or latents.shape[1] != self.cfg.latent_channels:

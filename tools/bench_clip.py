@@ -17,25 +17,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from leco_amd import clip as CL  # noqa: E402
+from tools.timing import print_per_op, time_ms  # noqa: E402
 
 MODELS = {"clip_l": (CL.clip_l_config, False), "open_clip_h": (CL.open_clip_h_config, False), "bigg": (CL.open_clip_bigg_config, True)}
 VOCAB = 4096
-
-
-def _time(fn, iters):
-    for _ in range(2):
-        fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(iters):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        ts.append(e0.elapsed_time(e1))
-    ts.sort()
-    return ts[len(ts) // 2], ts[0], ts[-1]
 
 
 def main(argv=None):
@@ -65,24 +50,17 @@ def main(argv=None):
                 model.use_graphs = graphs
                 model(ids)                               # builds the plan (and captures)
                 plan = model.engine().plan(B, 77)
-                med, lo, hi = _time(lambda: model._run(plan), args.iters)
+                med, lo, hi = time_ms(lambda: model._run(plan), args.iters)
                 line += f"  native {'graph' if graphs else 'eager'} {med:.3f} ({lo:.3f} .. {hi:.3f})"
             line += f"  launches {len(plan.ops)}"
             if not args.no_torch:
                 idd = ids.to(dev)
                 with torch.no_grad():
-                    med, lo, hi = _time(lambda: clip_ref(sd, cfg, idd, torch.bfloat16), args.iters)
+                    med, lo, hi = time_ms(lambda: clip_ref(sd, cfg, idd, torch.bfloat16), args.iters)
                 line += f"  torch bf16 eager {med:.3f} ({lo:.3f} .. {hi:.3f})"
             print(line, flush=True)
             if args.per_op:
-                kinds = {}
-                for label, op in zip(plan.names, plan.ops):
-                    med, _, _ = _time(lambda: op.run(), 5)
-                    t, n = kinds.get(label, (0.0, 0))
-                    kinds[label] = (t + med, n + 1)
-                tot = sum(t for t, _ in kinds.values())
-                for label, (t, n) in sorted(kinds.items(), key=lambda kv: -kv[1][0]):
-                    print(f"    {t:8.3f} ms {100 * t / tot:5.1f} %  {label} x {n}  ({1e3 * t / n:.1f} us each, launched one at a time)")
+                print_per_op(plan)
         model.release()
         del model, sd
         torch.cuda.empty_cache()

@@ -17,22 +17,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from leco_amd import model_util  # noqa: E402
-
-
-def _time(fn, iters):
-    for _ in range(2):
-        fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(iters):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        ts.append(e0.elapsed_time(e1))
-    ts.sort()
-    return ts[len(ts) // 2], ts[0], ts[-1]
+from tools.timing import print_per_op, time_ms  # noqa: E402
 
 
 def _transformers_model(model, dev):
@@ -76,24 +61,17 @@ def main(argv=None):
             model.use_graphs = graphs
             model.encode_images(img)                 # builds the plan (and captures)
             plan = model.engine().plan(B, (args.size, args.size))
-            med, lo, hi = _time(lambda: model._run(plan), args.iters)
+            med, lo, hi = time_ms(lambda: model._run(plan), args.iters)
             line += f"  native {'graph' if graphs else 'eager'} {med:.3f} ({lo:.3f} .. {hi:.3f})"
         line += f"  launches {len(plan.ops)}"
         if hf is not None:
             px = torch.randn(B, 3, cfg.image_size, cfg.image_size, device=dev, dtype=torch.bfloat16)
             with torch.no_grad():
-                med, lo, hi = _time(lambda: hf(pixel_values=px).image_embeds, args.iters)
+                med, lo, hi = time_ms(lambda: hf(pixel_values=px).image_embeds, args.iters)
             line += f"  transformers bf16 eager (preprocessed pixels) {med:.3f} ({lo:.3f} .. {hi:.3f})"
         print(line, flush=True)
         if args.per_op:
-            kinds = {}
-            for label, op in zip(plan.names, plan.ops):
-                med, _, _ = _time(lambda: op.run(), 5)
-                t, n = kinds.get(label, (0.0, 0))
-                kinds[label] = (t + med, n + 1)
-            tot = sum(t for t, _ in kinds.values())
-            for label, (t, n) in sorted(kinds.items(), key=lambda kv: -kv[1][0]):
-                print(f"    {t:8.3f} ms {100 * t / tot:5.1f} %  {label} x {n}  ({1e3 * t / n:.1f} us each, launched one at a time)")
+            print_per_op(plan)
     model.release()
 
 

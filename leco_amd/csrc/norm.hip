@@ -18,23 +18,11 @@
 #include <leco_prims.h>
 
 #include "common.h"
+#include "vec8.h"
 
 namespace leco {
 namespace {
 
-__device__ __forceinline__ void unpack8(const u32x4& v, float (&f)[8]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        f[2 * i] = bf2f((bf16_t)(v[i] & 0xffffu));
-        f[2 * i + 1] = bf2f((bf16_t)(v[i] >> 16));
-    }
-}
-__device__ __forceinline__ u32x4 pack8(const float (&f)[8]) {
-    u32x4 v;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = pack_bf2(f[2 * i], f[2 * i + 1]);
-    return v;
-}
 // z sigmoid(z) with the hardware reciprocal (v_rcp_f32, 1 ulp) and exp2: the IEEE fp32 division of `z / (1 + expf(-z))` is a
 // ten-instruction sequence per element, and the GroupNorm launches of the 32^2 / 64^2 levels are VALU-bound on it (round 6)
 __device__ __forceinline__ float silu(float z) { return z * fast_rcp(1.f + fast_exp2(-1.4426950408889634f * z)); }

@@ -480,6 +480,22 @@ enum { LECO_PRODIGY_DECOUPLE = 1, LECO_PRODIGY_BIAS_CORRECTION = 2, LECO_PRODIGY
 int leco_prodigy(float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* s, const float* p0, void* shadow,
                  const float* hyper, leco_prodigy_state* state, double beta1, double beta2, double beta3, double eps,
                  double weight_decay, double d_coef, double growth_rate, int32_t flags, int64_t n, leco_stream_t stream);
+/* Global L2 norm of grad_scale * g over the flat gradient slab, and clipping through the optimizer's own grad_scale: runs
+ * between the upload of `hyper` and leco_adamw / leco_lion / leco_prodigy, which read hyper[3] -- they need no change.
+ * hyper: the optimizers' device block {lr, bc1, bc2, grad_scale}.
+ * stats (device fp32[4]): {norm, coef, number of non-finite elements (inf or NaN bit patterns of g), 0}.
+ *   norm = sqrt(sum_e ((double)g[e] * (double)hyper[3])^2), accumulated in double
+ *   coef = max_norm > 0 ? min(1, max_norm / (norm + 1e-6)) : 1     (torch.nn.utils.clip_grad_norm_'s arithmetic, in double;
+ *          max_norm = 0: measure only; 1 as well when a non-finite element was seen: nothing is scaled then)
+ *   hyper[3] <- (float)((double)hyper[3] * coef)   -- NOT written when coef == 1 or when a non-finite element was seen
+ * One pass over g, one launch, no host round trip.  Per-block double partials added in a fixed order by the last block to
+ * finish (the reduction of leco_prodigy): bitwise reproducible, so data-parallel replicas derive the same coef.  The
+ * scratch is per device: launches on one device must be stream-ordered.  -EINVAL: a null operand, n <= 0, max_norm
+ * negative or NaN. */
+int leco_grad_clip(const float* g, int64_t n, float* hyper, float max_norm, float* stats, leco_stream_t stream);
+/* acc = first ? g : acc + g  (fp32, elementwise; acc is not read when first != 0).  One launch per micro-step of a
+ * gradient-accumulation group. */
+int leco_grad_accumulate(float* acc, const float* g, int64_t n, int32_t first, leco_stream_t stream);
 int leco_cast_f32_bf16(const float* x, void* y, int64_t n, leco_stream_t stream);
 int leco_memset(void* p, int32_t value, int64_t bytes, leco_stream_t stream);
 /* dst = `reps` copies of the `bytes` (multiple of 16) at src, back to back: batch broadcast of a tensor that is identical for

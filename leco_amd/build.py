@@ -49,8 +49,17 @@ def build(verbose: bool = False) -> str:
 
 def _build_locked(verbose: bool) -> str:
 
+    def name(src):
+        return os.path.join(OBJ, os.path.basename(src) + "." + _digest(src) + ".o")
+
+    stamp = os.path.join(OBJ, "link.stamp")
+    # the library was linked from exactly the objects these sources hash to: nothing to do, even where the objects
+    # themselves did not travel with the tree
+    if os.path.exists(LIB) and os.path.exists(stamp) and open(stamp).read() == " ".join(name(s) for s in _sources()):
+        return LIB
+
     def one(src):
-        obj = os.path.join(OBJ, os.path.basename(src) + "." + _digest(src) + ".o")
+        obj = name(src)
         if not os.path.exists(obj):
             cmd = [HIPCC, *FLAGS, "-x", "hip", "-c", src, "-o", obj]
             if verbose:

@@ -8,7 +8,7 @@ from typing import Literal, Optional
 
 import torch
 import yaml
-from pydantic import BaseModel, model_validator
+from pydantic import BaseModel, model_serializer, model_validator
 
 from .lora import TRAINING_METHODS
 
@@ -51,6 +51,28 @@ class TrainConfig(BaseModel):
     optimizer_args: str = ""
     lr_scheduler: str = "constant"
     max_denoising_steps: int = 50
+    # extensions (the reference has neither): clip the LoRA gradient to this global L2 norm (0: measure and log only);
+    # apply the optimizer every N-th iteration on the mean gradient of the N prompt pairs drawn in between
+    max_grad_norm: Optional[float] = None
+    gradient_accumulation_steps: int = 1
+
+    @model_validator(mode="after")
+    def _gradient_controls(self):
+        if self.gradient_accumulation_steps < 1:
+            raise ValueError(f"train.gradient_accumulation_steps={self.gradient_accumulation_steps}: must be >= 1")
+        if self.max_grad_norm is not None and not self.max_grad_norm >= 0:
+            raise ValueError(f"train.max_grad_norm={self.max_grad_norm}: must be >= 0 (0: measure only)")
+        return self
+
+    @model_serializer(mode="wrap")
+    def _unset_extensions_stay_out_of_the_dump(self, handler):
+        # a config that does not use them dumps exactly the reference's keys (model_dump(), the metadata of a saved LoRA)
+        d = handler(self)
+        if self.max_grad_norm is None:
+            d.pop("max_grad_norm", None)
+        if self.gradient_accumulation_steps == 1:
+            d.pop("gradient_accumulation_steps", None)
+        return d
 
 
 class SaveConfig(BaseModel):

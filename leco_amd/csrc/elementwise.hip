@@ -1,7 +1,8 @@
 // HBM-bound elementwise / small kernels of the LECO step: GEGLU, row-strided adds, the per-sample LoRA row scales, 2x2
 // upsample dgrad, timestep sinusoid, CFG-combine + DDIM / scheduler update, ESD loss + its gradient, fused AdamW / Lion /
 // Prodigy, LoRA operand packing and weight gradients, per-sample column sums, and the copies / fills between launch plans.
-// (The thin 3x3 convolutions at the ends of the UNet and the VAE live in edge_conv.hip.)
+// (The thin 3x3 convolutions at the ends of the UNet and the VAE live in edge_conv.hip; gradient clipping and accumulation on
+// the slab in grad_clip.hip.)
 // All bf16 traffic is moved as 16-byte vectors (8 x bf16 per lane); latent-sized tensors
 // ((bs,4,h,w), a few hundred KB) stay fp32.
 #include <errno.h>
@@ -10,6 +11,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "reduce_f64.h"
 #include "vec8.h"
 
 namespace leco {
@@ -336,33 +338,10 @@ struct ProdigyConst {
     double beta1, beta2, beta3, eps, wd, d_coef, growth;
     int flags;
 };
-__device__ __forceinline__ double shfl_xor_f64(double v, int mask) {      // the two halves travel as bit patterns
-    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
-    const float lo = shfl_xor(__builtin_bit_cast(float, (unsigned)(u & 0xffffffffull)), mask);
-    const float hi = shfl_xor(__builtin_bit_cast(float, (unsigned)(u >> 32)), mask);
-    return __builtin_bit_cast(double, ((unsigned long long)__builtin_bit_cast(unsigned, hi) << 32) |
-                                          (unsigned long long)__builtin_bit_cast(unsigned, lo));
-}
 __device__ __forceinline__ double prodigy_dlr(const leco_prodigy_state* st, double lr, const ProdigyConst& c) {
     double bc = 1.0;
     if (c.flags & LECO_PRODIGY_BIAS_CORRECTION) bc = sqrt(1.0 - pow(c.beta2, st->k + 1.0)) / (1.0 - pow(c.beta1, st->k + 1.0));
     return st->d * lr * bc;
-}
-// sums of a and b over the 256 threads of the block, in a fixed order (xor butterfly in each wave, then the four wave totals);
-// the result is valid in thread 0
-__device__ __forceinline__ void prodigy_block_sum(double& a, double& b, double (&red)[2][4]) {
-#pragma unroll
-    for (int mk = 32; mk >= 1; mk >>= 1) {
-        a += shfl_xor_f64(a, mk);
-        b += shfl_xor_f64(b, mk);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        red[0][threadIdx.x >> 6] = a;
-        red[1][threadIdx.x >> 6] = b;
-    }
-    __syncthreads();
-    a = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-    b = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
 }
 __global__ __launch_bounds__(256) void prodigy_moments_kernel(const float* p, const float* g, float* m, float* v, float* s,
                                                                const float* p0, const float* hyper, leco_prodigy_state* st,
@@ -396,7 +375,7 @@ __global__ __launch_bounds__(256) void prodigy_moments_kernel(const float* p, co
             den += (double)fabsf(ss);
         }
     }
-    prodigy_block_sum(num, den, red);
+    block_sum_f64(num, den, red);
     if (threadIdx.x == 0) {
         g_prodigy_part[2 * blockIdx.x] = num;
         g_prodigy_part[2 * blockIdx.x + 1] = den;
@@ -415,7 +394,7 @@ __global__ __launch_bounds__(256) void prodigy_moments_kernel(const float* p, co
         td += ((volatile double*)g_prodigy_part)[2 * b + 1];
     }
     __syncthreads();                                                   // thread 0 is done with `red`
-    prodigy_block_sum(tn, td, red);
+    block_sum_f64(tn, td, red);
     if (threadIdx.x == 0) {           // every block has read the state before it drew its ticket: it may change now
         double d = st->d;
         const double dlr = coef[3];

@@ -58,6 +58,8 @@ _SIGS = {
     "leco_adamw": [_vp, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _i64, _vp],
     "leco_lion": [_vp, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _i64, _vp],
     "leco_prodigy": [_vp] * 9 + [_f64] * 7 + [_i32, _i64, _vp],
+    "leco_grad_clip": [_vp, _i64, _vp, _f32, _vp, _vp],
+    "leco_grad_accumulate": [_vp, _vp, _i64, _i32, _vp],
     "leco_cast_f32_bf16": [_vp, _vp, _i64, _vp],
     "leco_memset": [_vp, _i32, _i64, _vp],
     "leco_repeat": [_vp, _vp, _i64, _i32, _vp],
@@ -440,6 +442,22 @@ def prodigy(p, g, m, v, s, p0, shadow, hyper, state, beta1, beta2, beta3, eps, w
     return Op("leco_prodigy", (ptr(p), ptr(g), ptr(m), ptr(v), ptr(s), ptr(p0), ptr(shadow), ptr(hyper), ptr(state),
                                float(beta1), float(beta2), float(beta3), float(eps), float(wd), float(d_coef),
                                float(growth_rate), flags, n), keep=(s, p0, state))
+
+
+GRAD_STATS_FIELDS = ("norm", "coef", "nonfinite")          # stats[0..2] of leco_grad_clip
+
+
+def grad_clip(g, hyper, max_norm, stats, n) -> Op:
+    """norm of hyper[3] * g over the flat slab -> stats {norm, coef, non-finite count, 0}; hyper[3] *= coef when it clips
+    (``max_norm == 0``: measure only).  One launch, before the optimizer kernel that reads hyper[3]."""
+    if stats.dtype != torch.float32 or stats.numel() < 4 or hyper.dtype != torch.float32 or hyper.numel() < 4:
+        raise ValueError("grad_clip: hyper and stats must be 4 fp32 values each")
+    return Op("leco_grad_clip", (ptr(g), n, ptr(hyper), float(max_norm), ptr(stats)), keep=(g, hyper, stats))
+
+
+def grad_accumulate(acc, g, n, first) -> Op:
+    """acc = g (``first``) or acc + g: one micro-step of a gradient-accumulation group."""
+    return Op("leco_grad_accumulate", (ptr(acc), ptr(g), n, 1 if first else 0), keep=(acc, g))
 
 
 def cast_f32_bf16(x, y, n) -> Op:

@@ -19,6 +19,10 @@ save cadence and file names.  The per-step arithmetic (train_lora.py:141-290) is
   6. data parallel: ONE all-reduce (RCCL over xGMI) of that slab -- no other collective;
   7. fused AdamW (or Lion / Prodigy) on the flat fp32 master slab, refreshing the bf16 shadow the kernels read.
 
+Optional, both on the device: ``max_grad_norm`` clips the gradient by its global norm between 6 and 7 (one reduction launch
+that rewrites the optimizers' device-side grad_scale); ``accumulate`` = A sums the gradients of A steps in a second slab and
+runs 6 and 7 once per group.
+
 Nothing in a step synchronises with the host; ``loss`` is a device scalar.
 """
 from __future__ import annotations
@@ -126,12 +130,21 @@ class FusedStep:
 
     def __init__(self, unet, network: LoRANetwork, scheduler, max_denoising_steps: int = 50, lr: float = 1e-4,
                  betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, world_size: int = 1,
-                 process_group=None, optimizer="adamw", dedup: bool = False, prodigy: Optional[dict] = None):
+                 process_group=None, optimizer="adamw", dedup: bool = False, prodigy: Optional[dict] = None,
+                 max_grad_norm: Optional[float] = None, accumulate: int = 1):
         """``optimizer``: "adamw" / "adam" (fused leco_adamw; adam = no decoupled decay), "lion" (fused leco_lion),
         "prodigy" (fused leco_prodigy; ``prodigy``: its keywords, `PRODIGY_DEFAULTS` -- ``betas`` / ``eps`` default to
         this constructor's arguments, ``weight_decay`` to Prodigy's own 0 unless the dict carries it; ``lr`` is the
         multiplier of the estimated step size, normally 1.0), or a ``torch.optim.Optimizer`` built on ``network.prepare_optimizer_params()`` (its ``step()``
-        runs on the fp32 slab views, then the bf16 shadow is refreshed)."""
+        runs on the fp32 slab views, then the bf16 shadow is refreshed).
+        ``max_grad_norm``: clip the (all-reduced, averaged) gradient to this global L2 norm before the optimizer, on the
+        device (`leco_grad_clip` rewrites the optimizers' grad_scale); 0 = measure only (`grad_stats`); None = off, no launch.
+        ``accumulate`` = A > 1: `step` adds its gradient to ``network.grad_acc`` and only every A-th call all-reduces and
+        applies the optimizer, on the mean of the group (`flush` applies a partial group)."""
+        if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
+            raise ValueError(f"max_grad_norm must be >= 0 (0: measure only) or None, got {max_grad_norm!r}")
+        if int(accumulate) != accumulate or accumulate < 1:
+            raise ValueError(f"accumulate must be an integer >= 1, got {accumulate!r}")
         self.unet, self.net, self.sched = unet, network, scheduler
         self.optimizer = optimizer
         self.n_steps = max_denoising_steps
@@ -195,6 +208,12 @@ class FusedStep:
         self.dedup = bool(dedup)
         self.target_from_forward_only = False      # test hook, see `step`
         self._token = next(FusedStep._tokens)      # names this object's private launch lists on plans the engine shares by shape
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self._grad_stats = torch.zeros(4, dtype=torch.float32, device=dev) if max_grad_norm is not None else None
+        self.accumulate = int(accumulate)
+        self.pending = 0                           # micro-steps summed in network.grad_acc since the last optimizer step
+        if self.accumulate > 1:
+            self._grad_acc()
 
     # ---- host -> device copies that do not stall the host -------------------------------------------------------
     N_PIN = 4
@@ -501,6 +520,15 @@ class FusedStep:
         self._run(plan, "bwd")
         net.multiplier = 0  # the reference leaves the `with network:` block here
         trace.pop()
+        if self.accumulate > 1:
+            # 5b. gradient accumulation: this micro-step's gradient joins the group's sum; the all-reduce and the optimizer
+            # run once per group.  (Not by letting the backward add into a non-zero slab: the atomic wgrad path adds, the
+            # deterministic and fp32 reduce paths write.)
+            ops.grad_accumulate(self._grad_acc(), net.grad, net.grad.numel(), self.pending == 0).run()
+            self.pending += 1
+            if self.pending == self.accumulate:
+                self.flush(lr)
+            return self.loss
         # 6. data parallel: one all-reduce of the LoRA gradient slab
         if self.world > 1:
             import torch.distributed as dist
@@ -513,19 +541,50 @@ class FusedStep:
         trace.pop()
         return self.loss
 
-    def apply_optimizer(self, lr: Optional[float] = None) -> None:
-        """Step 7 of `step`: consume `network.grad` (already all-reduced) with the configured optimizer."""
+    def _grad_acc(self) -> torch.Tensor:
+        """`network.grad_acc`: the fp32 sum of a group's micro-step gradients (exists only when accumulate > 1)."""
+        net = self.net
+        acc = getattr(net, "grad_acc", None)
+        if acc is None or acc.shape != net.grad.shape or acc.device != net.grad.device:
+            acc = net.grad_acc = torch.zeros_like(net.grad)
+            self.pending = 0
+        return acc
+
+    def flush(self, lr: Optional[float] = None) -> None:
+        """Apply the pending group of c <= accumulate micro-steps: one all-reduce of `network.grad_acc`, then the optimizer
+        on its mean (grad_scale 1 / (world c)).  Nothing pending: nothing happens.  `step` calls it when a group is full;
+        call it after the last step of a run whose length is no multiple of `accumulate`.  Collective when data parallel."""
+        if self.pending == 0:
+            return
+        acc, count = self._grad_acc(), self.pending
+        if self.world > 1:
+            import torch.distributed as dist
+            trace.push("all_reduce LoRA gradients")
+            dist.all_reduce(acc, group=self.pg)
+            trace.pop()
+        trace.push("optimizer")
+        self.pending = 0
+        self.apply_optimizer(lr, grad=acc, count=count)
+        trace.pop()
+
+    def apply_optimizer(self, lr: Optional[float] = None, grad: Optional[torch.Tensor] = None, count: int = 1) -> None:
+        """Step 7 of `step`: consume `network.grad` (already all-reduced) with the configured optimizer.  ``grad`` /
+        ``count``: another slab of that size holding the sum of `count` micro-steps (`flush`)."""
         net = self.net
         self.opt_step += 1
         b1, b2 = self.betas
         lr = self.lr if lr is None else lr
-        self._h2d(net.hyper, torch.tensor([lr, 1 - b1 ** self.opt_step, 1 - b2 ** self.opt_step, 1.0 / self.world],
+        g = net.grad if grad is None else grad
+        self._h2d(net.hyper, torch.tensor([lr, 1 - b1 ** self.opt_step, 1 - b2 ** self.opt_step, 1.0 / (self.world * count)],
                                           dtype=torch.float32))
+        if self.max_grad_norm is not None:
+            # hyper[3] <- coef / (world count), on the device: the optimizer kernels below read it as their grad_scale
+            ops.grad_clip(g, net.hyper, self.max_grad_norm, self._grad_stats, net.slab.numel()).run()
         if isinstance(self.optimizer, str) and self.optimizer in ("adam", "adamw"):
-            ops.adamw(net.slab.detach(), net.grad, net.exp_avg, net.exp_avg_sq, net.shadow, net.hyper, b1, b2, self.eps,
+            ops.adamw(net.slab.detach(), g, net.exp_avg, net.exp_avg_sq, net.shadow, net.hyper, b1, b2, self.eps,
                       self.wd, net.slab.numel()).run()
         elif self.optimizer == "lion":
-            ops.lion(net.slab.detach(), net.grad, net.exp_avg, net.shadow, net.hyper, b1, b2, self.wd,
+            ops.lion(net.slab.detach(), g, net.exp_avg, net.shadow, net.hyper, b1, b2, self.wd,
                      net.slab.numel()).run()
         elif self.optimizer == "prodigy":
             c = self.prodigy
@@ -533,12 +592,16 @@ class FusedStep:
             if not self._prodigy_p0_taken:       # the first Prodigy step: x_0 of the distance estimate
                 p0.copy_(net.slab.detach())
                 self._prodigy_p0_taken = True
-            ops.prodigy(net.slab.detach(), net.grad, net.exp_avg, net.exp_avg_sq, s, p0, net.shadow, net.hyper, state,
+            ops.prodigy(net.slab.detach(), g, net.exp_avg, net.exp_avg_sq, s, p0, net.shadow, net.hyper, state,
                         c["betas"][0], c["betas"][1], c["beta3"], c["eps"], c["weight_decay"], c["d_coef"], c["growth_rate"],
                         c["decouple"], c["use_bias_correction"], c["safeguard_warmup"], net.slab.numel()).run()
         else:   # any torch optimizer over the slab views (prodigy, dadapt*, 8-bit ... when their packages exist)
-            if self.world > 1:
-                net.grad.mul_(1.0 / self.world)
+            if g is not net.grad:             # the optimizer objects read `network.grad` (their .grad views / the strict copy)
+                net.grad.copy_(g)
+            if self.max_grad_norm is not None:
+                net.grad.mul_(net.hyper[3])      # the device scalar coef / (world count): no host synchronisation
+            elif self.world * count > 1:
+                net.grad.mul_(1.0 / (self.world * count))
             if not isinstance(self.optimizer, StrictReferenceOptimizer):
                 net.attach_grads()
             for group in self.optimizer.param_groups:
@@ -546,6 +609,15 @@ class FusedStep:
             self.optimizer.step()
             net.sync_shadow()
         net.mark_updated()
+
+    def grad_stats(self) -> dict:
+        """{norm, coef, nonfinite} of the last optimizer step's gradient (`leco_grad_clip`: the norm of the averaged,
+        all-reduced gradient before clipping, the factor applied, the number of inf / NaN elements).  Copies them from the
+        device, i.e. waits for the queued steps: for tests and logging."""
+        if self._grad_stats is None:
+            raise RuntimeError("this FusedStep was built without max_grad_norm (0 measures without clipping)")
+        norm, coef, bad, _ = self._grad_stats.cpu().tolist()
+        return dict(zip(ops.GRAD_STATS_FIELDS, (norm, coef, int(bad))))
 
     def _prodigy_buffers(self):
         """Prodigy's slab-sized `s` and `p0` and its device scalar state (ops.prodigy_state)."""
@@ -593,6 +665,12 @@ def save_training_state(path, fused: "FusedStep", iteration: int, lr_scheduler=N
         rank = dist.get_rank(fused.pg)
         rngs = [None] * fused.world
         dist.all_gather_object(rngs, _rank_rng_states(fused.dev), group=fused.pg)
+    accs = None
+    if fused.pending:                # (the same count on every rank: they run the same loop)
+        accs = [fused._grad_acc().cpu().clone()]
+        if fused.world > 1:
+            mine, accs = accs[0], [None] * fused.world
+            dist.all_gather_object(accs, mine, group=fused.pg)
     if rank != 0:
         return
     blob = {k: getattr(net, k).detach().cpu().clone() for k in STATE_KEYS}
@@ -604,6 +682,8 @@ def save_training_state(path, fused: "FusedStep", iteration: int, lr_scheduler=N
         if not fused._prodigy_p0_taken:      # saved before the first step: x_0 is the slab as it stands
             p0 = net.slab.detach()
         blob.update(format=3, prodigy=dict(s=s.cpu().clone(), p0=p0.cpu().clone(), state=state.cpu().clone()))
+    if accs is not None:             # saved inside an accumulation group: every rank's partial sum (files saved on a group boundary stay as they were)
+        blob.update(format=4, grad_acc=torch.stack(accs), pending=int(fused.pending), accumulate=int(fused.accumulate))
     torch.save(blob, path)
 
 
@@ -640,9 +720,26 @@ def load_training_state(path, fused: "FusedStep", lr_scheduler=None) -> int:
                 raise ValueError(f"{path}: prodigy.{k} has shape {tuple(pz[k].shape)}, the network's slab {tuple(net.slab.shape)}")
         if pz["state"].dtype != torch.float64 or pz["state"].numel() != len(ops.PRODIGY_STATE_FIELDS):
             raise ValueError(f"{path}: prodigy.state is not the {len(ops.PRODIGY_STATE_FIELDS)} doubles of leco_prodigy_state")
+    pending = int(blob.get("pending", 0))
+    if pending:
+        saved_acc = int(blob["accumulate"])
+        if saved_acc != fused.accumulate:
+            raise ValueError(f"{path}: saved inside an accumulation group ({pending} of {saved_acc} micro-steps pending); this run "
+                             f"accumulates {fused.accumulate}.  Resume with gradient_accumulation_steps: {saved_acc}.")
+        ga = blob["grad_acc"]
+        if tuple(ga.shape) != (fused.world, *net.grad.shape) or ga.dtype != torch.float32 or not 0 < pending < saved_acc:
+            raise ValueError(f"{path}: grad_acc has shape {tuple(ga.shape)} with {pending} pending micro-steps, expected "
+                             f"{(fused.world, *net.grad.shape)} and fewer than {saved_acc}")
+    rank = 0
+    if fused.world > 1:
+        import torch.distributed as dist
+        rank = dist.get_rank(fused.pg)
     with torch.no_grad():
         for k in STATE_KEYS:
             getattr(net, k).detach().copy_(blob[k].to(getattr(net, k).device))
+        if pending:
+            fused._grad_acc().copy_(blob["grad_acc"][rank].to(net.grad.device))
+        fused.pending = pending
         if pz is not None:
             for dst, k in zip(fused._prodigy_buffers(), ("s", "p0", "state")):
                 dst.copy_(pz[k].to(dst.device))
@@ -655,10 +752,6 @@ def load_training_state(path, fused: "FusedStep", lr_scheduler=None) -> int:
         # recursive schedules (cosine) continue from the optimizer's current lr, which the scheduler state lacks
         for group, lr in zip(lr_scheduler.optimizer.param_groups, lr_scheduler.get_last_lr()):
             group["lr"] = lr
-    rank = 0
-    if fused.world > 1:
-        import torch.distributed as dist
-        rank = dist.get_rank(fused.pg)
     torch.set_rng_state(rngs[rank]["cpu"])
     if fused.dev.type == "cuda" and "cuda" in rngs[rank]:
         torch.cuda.set_rng_state(rngs[rank]["cuda"], fused.dev)
@@ -790,7 +883,8 @@ def train(config: RootConfig, prompts: List[PromptSettings], device: Optional[to
     fused = FusedStep(unet, network, noise_scheduler, config.train.max_denoising_steps, lr=config.train.lr,
                       betas=tuple(optimizer_kwargs.get("betas", default_betas)), eps=optimizer_kwargs.get("eps", 1e-8),
                       weight_decay=optimizer_kwargs.get("weight_decay", wd_default), world_size=world,
-                      optimizer=fused_opt, dedup=dedup,
+                      optimizer=fused_opt, dedup=dedup, max_grad_norm=config.train.max_grad_norm,
+                      accumulate=config.train.gradient_accumulation_steps,
                       prodigy={k: v for k, v in optimizer_kwargs.items() if k not in ("betas", "eps")}
                       if fused_opt == "prodigy" else None)
     # LR schedule: drive torch's own scheduler objects on a dummy parameter so the values are exact
@@ -847,6 +941,7 @@ def train(config: RootConfig, prompts: List[PromptSettings], device: Optional[to
             hw = train_util.get_random_resolution_in_bucket(lead.resolution, generator=shape_gen)
         return k, shape_class(lead), hw
     loss = None
+    lr_now = config.train.lr
     start = 0
     if resume_from is not None:
         start = load_training_state(resume_from, fused, lr_scheduler)
@@ -874,15 +969,25 @@ def train(config: RootConfig, prompts: List[PromptSettings], device: Optional[to
                   pair.dynamic_resolution, (height, width), "batch_size:", pair.batch_size)
         latents = train_util.get_initial_latents(noise_scheduler, pair.batch_size, height, width, 1)
         add_time_ids = train_util.get_add_time_ids(height, width, dynamic_crops=pair.dynamic_crops) if xl else None
-        loss = fused.step(pair, timesteps_to, latents, lr=lr_scheduler.get_last_lr()[0], add_time_ids=add_time_ids)
+        lr_now = lr_scheduler.get_last_lr()[0]
+        loss = fused.step(pair, timesteps_to, latents, lr=lr_now, add_time_ids=add_time_ids)
         show = pbar is not None and (i % 10 == 0 or config.logging.verbose)
         # (the loss already waits for the step where it is shown: Prodigy's estimated step size d * lr comes along, fetched once)
         dlr = fused.prodigy_state()["dlr"] if fused.prodigy and (show or wandb is not None) else None
+        # ... and, when clipping is configured, the norm of the last applied gradient.  Non-finite gradients are DETECTED here,
+        # i.e. as coarsely as the loss is shown (every 10th iteration unless verbose, every iteration with wandb): the step
+        # itself never meets the host, and no step is skipped.
+        gstat = fused.grad_stats() if fused.max_grad_norm is not None and fused.opt_step and (show or wandb is not None) else None
+        if gstat is not None and gstat["nonfinite"] > 0:
+            raise FloatingPointError(f"iteration {i}: {gstat['nonfinite']} non-finite element(s) in the LoRA gradient of the last "
+                                     f"optimizer step (norm {gstat['norm']}); the weights are no longer usable")
         if show:
-            pbar.set_description(f"Loss*1k: {loss.item() * 1000:.4f}" + ("" if dlr is None else f" d*lr: {dlr:.3e}"))
+            pbar.set_description(f"Loss*1k: {loss.item() * 1000:.4f}" + ("" if dlr is None else f" d*lr: {dlr:.3e}")
+                                 + ("" if gstat is None else f" |g|: {gstat['norm']:.2e}" + ("*" if gstat["coef"] < 1 else "")))
         if wandb is not None:
             wandb.log({"loss": loss.item(), "iteration": i, "lr": lr_scheduler.get_last_lr()[0],
-                       **({} if dlr is None else {"d*lr": dlr})})
+                       **({} if dlr is None else {"d*lr": dlr}),
+                       **({} if gstat is None else {"grad_norm": gstat["norm"], "clip_coef": gstat["coef"]})})
         _dummy.step()
         lr_scheduler.step()
         if i % config.save.per_steps == 0 and i != 0 and i != config.train.iterations - 1:
@@ -899,6 +1004,7 @@ def train(config: RootConfig, prompts: List[PromptSettings], device: Optional[to
                     save_path.mkdir(parents=True, exist_ok=True)
                 save_training_state(save_path / f"{config.save.name}_state.pt", fused, i, lr_scheduler)
             break
+    fused.flush(lr_now)      # a trailing partial accumulation group (nothing pending: no-op)
     if rank == 0:
         print("Saving...")
         save_path.mkdir(parents=True, exist_ok=True)

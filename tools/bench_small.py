@@ -1,7 +1,8 @@
 """Times a few small launches in isolation (HIP events over back-to-back repeats): conv_in / conv_out at the level-0 shape,
-self-attention forward, and the slab optimizers (leco_adamw / leco_prodigy from a replayed graph).
+self-attention forward, the slab optimizers (leco_adamw / leco_prodigy from a replayed graph) and the gradient controls
+(leco_grad_clip / leco_grad_accumulate beside leco_adamw).
     python tools/bench_small.py          (under `rocprofv3 --kernel-trace --stats` the kernel names show which path ran)
-    python tools/bench_small.py optimizers          only that section (also: conv, attention)"""
+    python tools/bench_small.py optimizers          only that section (also: conv, attention, grad_controls)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -92,6 +93,38 @@ def bench_optimizers():
         assert torch.isfinite(p).all()
 
 
-SECTIONS = {"conv": bench_conv, "attention": bench_attention, "optimizers": bench_optimizers}
+def slab_numel(kind, rank, c3lier):
+    """Floats in the LoRA slab of a BASELINE config: `net.slab.numel()` of its network, from a shape-only (meta) instance."""
+    import contextlib, io
+    from leco_amd import model_util
+    from leco_amd.lora import DEFAULT_TARGET_REPLACE, UNET_TARGET_REPLACE_MODULE_CONV, LoRANetwork
+    from leco_amd.unet import UNet2DConditionModel
+    with torch.device("meta"), contextlib.redirect_stdout(io.StringIO()):
+        net = LoRANetwork(UNet2DConditionModel(model_util.SYNTHETIC[kind]()), rank=rank,
+                          target_replace_modules=list(DEFAULT_TARGET_REPLACE) + (UNET_TARGET_REPLACE_MODULE_CONV if c3lier else []))
+    return net.numel + (-net.numel) % 64          # the slab is padded to 64 floats (LoRANetwork._build_slab)
+
+
+def bench_grad_controls():
+    """leco_grad_clip (reads g: 4 B/element; max_norm = 1.0 against a norm of ~1.3 / ~7: it clips) and leco_grad_accumulate
+    (first = 0: reads acc and g, writes acc = 12 B/element) beside leco_adamw (30 B/element) at the slab sizes of the SD1.5
+    rank-4 lierla and the SDXL rank-16 c3lier configs, one launch and 8 launches per graph replay."""
+    print("launch                  floats   us (graph of 1)   us (graph of 8)   bytes/elt   TB/s (graph of 8)")
+    for kind, rank, c3 in (("sd15", 4, False), ("sdxl", 16, True)):
+        n = slab_numel(kind, rank, c3)
+        p = torch.randn(n, device=dev) * 0.05; g = torch.randn(n, device=dev) * 1e-3; acc = torch.zeros(n, device=dev)
+        m = torch.zeros(n, device=dev); v = torch.zeros(n, device=dev); sh = torch.zeros(n, device=dev, dtype=bf)
+        hyper = torch.tensor([1e-4, 0.1, 0.001, 1.0], device=dev); stats = torch.zeros(4, device=dev)
+        # (every clipping launch multiplies hyper[3] once more; the traffic does not depend on it)
+        rows = (("leco_adamw", [ops.adamw(p, g, m, v, sh, hyper, 0.9, 0.999, 1e-8, 1e-2, n)], 30),
+                ("leco_grad_clip", [ops.grad_clip(g, hyper, 1.0, stats, n)], 4),
+                ("leco_grad_accumulate", [ops.grad_accumulate(acc, g, n, False)], 12))
+        for name, op_list, bpe in rows:
+            t1, t8 = timeit_graph(op_list, 1), timeit_graph(op_list, 8)
+            print(f"{name:21s} {n:9d}   {t1:10.1f}        {t8:10.1f}        {bpe:3d}         {n * bpe / t8 / 1e6:6.2f}")
+        print(f"  grad_stats {dict(zip(ops.GRAD_STATS_FIELDS, stats.cpu().tolist()))}")
+
+
+SECTIONS = {"conv": bench_conv, "attention": bench_attention, "optimizers": bench_optimizers, "grad_controls": bench_grad_controls}
 for name in sys.argv[1:] or list(SECTIONS):
     SECTIONS[name]()

@@ -35,6 +35,10 @@ line per picture, with its strengths in a sweep, and the same table in `<image s
 `--attn_map WORD` (repeatable, needs `--image`) draws where in the picture WORD of the prompt acts: the cross-attention heat of
 its tokens over every decoded picture (`<image stem>.attn.png`, the layout of `--image` once per word, top to bottom) and the
 mean heat per cell in `<image stem>.attn.json`; `#3` / `#3-5` name raw token positions (`_attn_map.py`).
+
+`--image_diff [BASE]` (needs `--image`) says what else changed: SSIM, PSNR and MSE of every decoded picture against a baseline
+-- the all-zero cell of `--lora_scales` by default, another cell named by its strengths (`-1`, `0,1`), or a PNG of the same
+size -- in `<image stem>.diff.json`, and the change maps 1 - ssim over the pictures in `<image stem>.diff.png` (`_image_diff.py`).
 """
 import argparse
 import contextlib
@@ -49,6 +53,7 @@ sys.path[:0] = [os.path.dirname(HERE), HERE]
 from leco_amd import model_util, train_util  # noqa: E402
 import _attn_map  # noqa: E402
 import _clip_score  # noqa: E402
+import _image_diff  # noqa: E402
 import _lora_sweep  # noqa: E402
 from _img2img import init_latents  # noqa: E402
 
@@ -78,10 +83,12 @@ def main(argv=None):
                     help="encode the prompts with the native CLIP text encoder (leco_amd.clip, bf16 only) instead of transformers")
     _clip_score.add_arguments(ap)
     _attn_map.add_arguments(ap)
-    args = ap.parse_args(_lora_sweep.join_scales(argv))
+    _image_diff.add_arguments(ap)
+    args = ap.parse_args(_image_diff.join_base(_lora_sweep.join_scales(argv)))
     scales = _lora_sweep.parse_scales(ap, args)
     _clip_score.check(ap, args)
     _attn_map.check(ap, args)
+    _image_diff.check(ap, args, scales)
     n = 1 if scales is None else len(scales)
     dev = torch.device(args.device)
     dtype = torch.bfloat16
@@ -125,6 +132,7 @@ def main(argv=None):
     print(f"Done. latents {tuple(latents.shape)} -> {args.out}")
     score = _clip_score.hook(args, scales, dev, use_graphs=unet.use_graphs)
     score = _attn_map.hook(args, scales, unet, amap, cols=args.sheet_cols, also=score)
+    score = _image_diff.hook(args, scales, cols=args.sheet_cols, also=score)
     if args.image and scales is None:
         write_image(latents, args.vae or args.model, args.image, dev, use_graphs=unet.use_graphs, on_pictures=score)
     elif args.image:

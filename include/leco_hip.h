@@ -366,6 +366,34 @@ int leco_attn_maps_merge(const leco_attn_map_layer* layers, int32_t n_layers, fl
 int leco_heat_overlay(const float* heat, const float* rmax, const void* pic, const void* lut, void* out, int32_t batch,
                       int32_t n_maps, int32_t map_index, int32_t ht, int32_t wt, float alpha, leco_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Picture against picture: SSIM, squared error, change map (leco_amd/image_metrics.py; csrc/image_metrics.hip).
+ * ---------------------------------------------------------------------- */
+/* a: uint8 NHWC [batch][h][w][3]; ref: the same layout, picture b read at ref + b * ref_stride BYTES: ref_stride = 0 compares
+ * every picture with ONE baseline, ref_stride = h * w * 3 compares pairwise.  taps: DEVICE fp32 [11], the normalised
+ * Gaussian window (sigma = 1.5) computed on the host in float64 and rounded once (`image_metrics.gaussian_taps`); the window
+ * is symmetric and taps[0..5] are what is read; no exp is evaluated on the device.
+ * SSIM is Wang et al. 2004: per channel, the 11 x 11 separable window, biased moments, C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2,
+ *   ssim = (2 ma mr + C1)(2 sar + C2) / ((ma^2 + mr^2 + C1)(saa + srr + C2)),
+ * a pixel's value = the mean over the three channels, defined on the valid region only: the (h - 10) x (w - 10) pixels whose
+ * whole window lies inside the picture.
+ *   stats: DEVICE double [batch][2]; stats[b][0] = the mean SSIM over the valid region, stats[b][1] = the sum over ALL pixels
+ *     and channels of (a - ref)^2, an exact integer (PSNR and MSE are the host's to derive);
+ *   change_map (may be NULL): fp32 [batch][h][w] = 1 - ssim at the window's centre on the valid region, exactly 0 on the
+ *     5-pixel border.  It is not clamped: rounding can leave a value a few 1e-7 below 0.
+ * The moments are formed from centred levels (level - 128) in fp64; against a float64 statement with float64 taps an SSIM
+ * value differs by at most 5e-4 (the rounding of the taps to fp32; DESIGN.md, "Image metrics").  a == ref gives a mean SSIM of
+ * exactly 1.0 and a change map of exactly 0.  Every output element has one owner, the per-picture sums are added from
+ * per-workgroup partials in a fixed order by a second launch: no atomics, two runs give equal bits.
+ * workspace: DEVICE scratch of at least leco_image_compare_workspace(batch, h, w) bytes, 8-byte aligned; no state is kept in
+ * it between calls.  h < 11, w < 11, batch < 1 (or > 65535), a ref_stride that is neither 0 nor h * w * 3, or a workspace
+ * that is too small: -EINVAL with leco_last_error set, and nothing is launched. */
+int leco_image_compare(const void* a, const void* ref, int64_t ref_stride, int32_t batch, int32_t h, int32_t w,
+                       const float* taps, float* change_map, double* stats, void* workspace, int64_t workspace_bytes,
+                       leco_stream_t stream);
+/* bytes of workspace leco_image_compare needs (0 for arguments it refuses) */
+int64_t leco_image_compare_workspace(int32_t batch, int32_t h, int32_t w);
+
 /* GEGLU (diffusers FeedForward ff.net.0): y[m][f] = u[m][f] * gelu_erf(u[m][F+f]) */
 int leco_geglu_fwd(const void* u, int64_t ldu, void* y, int64_t ldy, int32_t m, int32_t f,
                    leco_stream_t stream);

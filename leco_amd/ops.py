@@ -37,6 +37,7 @@ _SIGS = {
     "leco_xattn_token_maps": [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp],
     "leco_attn_maps_merge": [_vp, _i32, _vp, _i32, _i32, _i32, _vp],
     "leco_heat_overlay": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp],
+    "leco_image_compare": [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp],
     "leco_gemm_ex": [C.POINTER(GemmArgs), _i32, _i32, _vp, _i64, _vp],
     "leco_geglu_fwd": [_vp, _i64, _vp, _i64, _i32, _i32, _vp],
     "leco_geglu_bwd": [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp],
@@ -333,6 +334,27 @@ def heat_overlay(heat, rmax, pic, lut, out, batch, n_maps, map_index, ht, wt, al
     over them through the colour table ``lut`` (uint8 [256][3]); ``rmax``: fp32 [batch * n_maps] reciprocal full-heat values."""
     return Op("leco_heat_overlay", (ptr(heat), ptr(rmax), ptr(pic), ptr(lut), ptr(out), batch, n_maps, map_index, ht, wt, float(alpha)),
               keep=(heat, rmax, pic, lut, out))
+
+
+def image_compare_workspace(batch: int, h: int, w: int) -> int:
+    """Bytes of scratch `image_compare` needs (0 for shapes it refuses)."""
+    fn = getattr(hip.lib(), "leco_image_compare_workspace")
+    fn.argtypes, fn.restype = [_i32, _i32, _i32], _i64
+    return int(fn(batch, h, w))
+
+
+def image_compare(a, ref, ref_stride, batch, h, w, taps, change_map, stats, workspace=None, workspace_bytes=None, keep=None) -> Op:
+    """Mean SSIM, exact SSE and (``change_map`` not None) the map 1 - ssim of the uint8 NHWC pictures ``a`` [batch][h][w][3]
+    against ``ref`` (``ref_stride`` bytes between its pictures: 0 = one baseline for all, h * w * 3 = pairwise); ``taps`` fp32
+    [11], ``stats`` float64 [batch][2] = (mean SSIM, SSE), ``change_map`` fp32 [batch][h][w]: DEVICE tensors or raw addresses
+    (include/leco_hip.h).  ``workspace``: a DEVICE buffer of `image_compare_workspace` bytes (its size is taken from the
+    tensor unless ``workspace_bytes`` says otherwise); None: one is allocated on ``stats``' device and kept by the Op."""
+    if workspace is None:
+        workspace = torch.empty(max(image_compare_workspace(batch, h, w), 8) // 8, dtype=torch.float64, device=stats.device)
+    if workspace_bytes is None:
+        workspace_bytes = workspace.numel() * workspace.element_size()
+    return Op("leco_image_compare", (ptr(a), ptr(ref), int(ref_stride), batch, h, w, ptr(taps), ptr(change_map), ptr(stats),
+                                     ptr(workspace), int(workspace_bytes)), keep=(a, ref, taps, change_map, stats, workspace, keep))
 
 
 def geglu_fwd(u, ldu, y, ldy, m, f) -> Op:

@@ -524,6 +524,30 @@ int leco_grad_clip(const float* g, int64_t n, float* hyper, float max_norm, floa
 /* acc = first ? g : acc + g  (fp32, elementwise; acc is not read when first != 0).  One launch per micro-step of a
  * gradient-accumulation group. */
 int leco_grad_accumulate(float* acc, const float* g, int64_t n, int32_t first, leco_stream_t stream);
+/* One LoRA module of the slab, for leco_lora_max_norm: lora_down = slab[down_off ..] as [r][k] (k = in_features, or
+ * in * kh * kw of a convolution), lora_up = slab[up_off ..] as [n][r], both row-major; r is the module's own rank (after
+ * the clamp of a narrow convolution), scale = alpha / r.  Offsets are in elements and need no alignment. */
+typedef struct leco_lora_norm_module {
+    int64_t down_off, up_off;
+    int32_t r, k, n;
+    float scale;
+} leco_lora_norm_module;
+/* Max-norm regularisation of the LoRA weights (train.scale_weight_norms), after the optimizer step, in one launch.
+ * table: M modules, in DEVICE memory; slab / shadow: the fp32 master slab of n elements and its bf16 shadow.  Per module m
+ *   norm_m  = scale_m * |up_m down_m|_F   from the two r x r Gram matrices, |U D|_F^2 = sum_ij (U^T U)_ij (D D^T)_ij,
+ *             accumulated in double from the fp32 slab; the multiplier is not part of it
+ *   ratio_m = norm_m <= max_norm ? 1 : max_norm / norm_m          (max_norm = 0: measure only, every ratio is 1)
+ *   f_m     = (float)sqrt(ratio_m), the square root in double; where ratio_m < 1 every element of lora_down and lora_up is
+ *             multiplied by f_m in fp32 in place and its shadow element rewritten with the optimizers' rounding (f2bf).
+ *             Modules with ratio_m = 1 are not written at all.
+ * A module whose norm is not finite (or whose table row does not lie inside the n elements) is left alone and counted.
+ * Outputs (device fp32): norms[M] before scaling, factors[M] = f_m (exactly 1 where nothing was scaled), stats[4] =
+ * {modules scaled, mean and maximum of norm_m * ratio_m over the modules with a finite norm, modules with a non-finite norm}.
+ * One workgroup per module; fixed summation orders and no floating-point atomics: bitwise reproducible.  The scratch of
+ * the statistics is per device: launches on one device must be stream-ordered.  -EINVAL: a null operand, n <= 0, M <= 0
+ * or M > 8192, max_norm negative or NaN. */
+int leco_lora_max_norm(float* slab, void* shadow, int64_t n, const leco_lora_norm_module* table, int32_t M, float max_norm,
+                       float* norms, float* factors, float* stats, leco_stream_t stream);
 int leco_cast_f32_bf16(const float* x, void* y, int64_t n, leco_stream_t stream);
 int leco_memset(void* p, int32_t value, int64_t bytes, leco_stream_t stream);
 /* dst = `reps` copies of the `bytes` (multiple of 16) at src, back to back: batch broadcast of a tensor that is identical for

@@ -55,6 +55,9 @@ class TrainConfig(BaseModel):
     # apply the optimizer every N-th iteration on the mean gradient of the N prompt pairs drawn in between
     max_grad_norm: Optional[float] = None
     gradient_accumulation_steps: int = 1
+    # extension: max-norm regularisation -- after every optimizer step, scale each LoRA module whose effective update
+    # (alpha / rank) * up @ down has a Frobenius norm above this bound back onto it (0: measure and log only)
+    scale_weight_norms: Optional[float] = None
 
     @model_validator(mode="after")
     def _gradient_controls(self):
@@ -62,6 +65,8 @@ class TrainConfig(BaseModel):
             raise ValueError(f"train.gradient_accumulation_steps={self.gradient_accumulation_steps}: must be >= 1")
         if self.max_grad_norm is not None and not self.max_grad_norm >= 0:
             raise ValueError(f"train.max_grad_norm={self.max_grad_norm}: must be >= 0 (0: measure only)")
+        if self.scale_weight_norms is not None and not self.scale_weight_norms >= 0:
+            raise ValueError(f"train.scale_weight_norms={self.scale_weight_norms}: must be >= 0 (0: measure only)")
         return self
 
     @model_serializer(mode="wrap")
@@ -72,6 +77,8 @@ class TrainConfig(BaseModel):
             d.pop("max_grad_norm", None)
         if self.gradient_accumulation_steps == 1:
             d.pop("gradient_accumulation_steps", None)
+        if self.scale_weight_norms is None:
+            d.pop("scale_weight_norms", None)
         return d
 
 

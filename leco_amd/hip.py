@@ -59,6 +59,11 @@ class WgradProblem(C.Structure):     # mirrors `leco_wgrad_problem` in include/l
     ]
 
 
+class LoraNormModule(C.Structure):   # mirrors `leco_lora_norm_module` (32 bytes: one row of the table of leco_lora_max_norm)
+    _fields_ = [("down_off", C.c_int64), ("up_off", C.c_int64), ("r", C.c_int32), ("k", C.c_int32), ("n", C.c_int32),
+                ("scale", C.c_float)]
+
+
 class XLin(C.Structure):          # mirrors `leco_xlin`
     _fields_ = [("w", C.c_void_p), ("ldw", C.c_int64), ("bias", C.c_void_p), ("dn", C.c_void_p), ("ld_dn", C.c_int64),
                 ("up", C.c_void_p), ("ld_up", C.c_int64), ("t_rows", C.c_int32), ("packed", C.c_int32)]

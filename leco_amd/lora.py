@@ -176,7 +176,50 @@ class LoRANetwork(nn.Module):
                 mod.weight.data = data[o:o + mod.weight.numel()].view(shape)
                 mod.weight.grad = None
             lora.alpha = lora.alpha.to(dev)
+        self._norm_buffers = None      # the device table of `weight_norms` / `apply_max_norm` follows the slab
         self.version += 1
+
+    # ---- max-norm regularisation (leco_lora_max_norm) --------------------------------------------------------------
+    def norm_buffers(self):
+        """(table, norms, factors, stats) of `leco_lora_max_norm` on the slab's device: the module table (offsets, each
+        module's own rank, K = the row length of `lora_down`, N = out, scale = alpha / r) uploaded once, and the kernel's
+        three fp32 outputs.  Built on first use and again when the slab is re-adopted (`to`)."""
+        if getattr(self, "_norm_buffers", None) is None:
+            dev = self.slab.device
+            rows = []
+            for lora in self.unet_loras:
+                dn, up = lora.lora_down.weight, lora.lora_up.weight
+                rows.append((lora.down_off, lora.up_off, dn.shape[0], dn.numel() // dn.shape[0], up.shape[0], lora.scale))
+            M = len(rows)
+            self._norm_buffers = (ops.lora_norm_table(rows, dev), torch.zeros(M, dtype=torch.float32, device=dev),
+                                  torch.ones(M, dtype=torch.float32, device=dev), torch.zeros(4, dtype=torch.float32, device=dev))
+        return self._norm_buffers
+
+    def _max_norm_op(self, max_norm: float):
+        if self.strict_reference:
+            raise ValueError("max-norm regularisation is not defined for --strict_reference networks (bf16 master weights)")
+        table, norms, factors, stats = self.norm_buffers()
+        return ops.lora_max_norm(self.slab.detach(), self.shadow, table, max_norm, norms, factors, stats)
+
+    def weight_norms(self) -> dict:
+        """{lora_name: scale * |lora_up lora_down|_F}: the Frobenius norm of every module's effective update at multiplier 1
+        (for a 3x3 `lora_down`: of the composed convolution).  One measure-only launch; waits for the device."""
+        self._max_norm_op(0.0).run()
+        norms = self.norm_buffers()[1].cpu().tolist()
+        return {lora.lora_name: v for lora, v in zip(self.unet_loras, norms)}
+
+    def apply_max_norm(self, max_norm: float) -> dict:
+        """Max-norm regularisation ("scale_weight_norms"): every module whose norm (`weight_norms`) exceeds ``max_norm`` has
+        `lora_down` and `lora_up` multiplied by sqrt(max_norm / norm) each, in the fp32 slab and its bf16 shadow.  Returns
+        ``dict(keys_scaled, avg_norm, max_norm, nonfinite)`` -- mean and maximum AFTER scaling over the modules with a
+        finite norm; modules with a non-finite norm are left alone and counted.  Waits for the device."""
+        if not float(max_norm) >= 0.0:
+            raise ValueError(f"apply_max_norm: max_norm must be >= 0 (0: measure only), got {max_norm!r}")
+        self._max_norm_op(float(max_norm)).run()
+        k, avg, top, bad = self.norm_buffers()[3].cpu().tolist()
+        if k > 0:
+            self.mark_updated()
+        return dict(zip(ops.WEIGHT_NORM_STATS_FIELDS, (int(k), avg, top, int(bad))))
 
     def to(self, *args, **kwargs):
         """Moves the slab; the fp32 master stays fp32 (the requested dtype only selects the

@@ -61,6 +61,7 @@ _SIGS = {
     "leco_prodigy": [_vp] * 9 + [_f64] * 7 + [_i32, _i64, _vp],
     "leco_grad_clip": [_vp, _i64, _vp, _f32, _vp, _vp],
     "leco_grad_accumulate": [_vp, _vp, _i64, _i32, _vp],
+    "leco_lora_max_norm": [_vp, _vp, _i64, _vp, _i32, _f32, _vp, _vp, _vp, _vp],
     "leco_cast_f32_bf16": [_vp, _vp, _i64, _vp],
     "leco_memset": [_vp, _i32, _i64, _vp],
     "leco_repeat": [_vp, _vp, _i64, _i32, _vp],
@@ -480,6 +481,35 @@ def grad_clip(g, hyper, max_norm, stats, n) -> Op:
 def grad_accumulate(acc, g, n, first) -> Op:
     """acc = g (``first``) or acc + g: one micro-step of a gradient-accumulation group."""
     return Op("leco_grad_accumulate", (ptr(acc), ptr(g), n, 1 if first else 0), keep=(acc, g))
+
+
+WEIGHT_NORM_STATS_FIELDS = ("keys_scaled", "avg_norm", "max_norm", "nonfinite")          # stats[0..3] of leco_lora_max_norm
+
+
+def lora_norm_table(modules, device) -> torch.Tensor:
+    """The module table of `leco_lora_max_norm` on ``device``: one `leco_lora_norm_module` (32 bytes) per entry of
+    ``modules``, each ``(down_off, up_off, r, k, n, scale)`` -- element offsets into the slab, `lora_down` = [r][k],
+    `lora_up` = [n][r].  Returned as a uint8 tensor of 32 * M bytes; uploaded once and reused by every launch."""
+    rows = (hip.LoraNormModule * len(modules))()
+    for row, (down_off, up_off, r, k, n, scale) in zip(rows, modules):
+        row.down_off, row.up_off, row.r, row.k, row.n, row.scale = int(down_off), int(up_off), int(r), int(k), int(n), float(scale)
+    return torch.frombuffer(bytearray(bytes(rows)), dtype=torch.uint8).to(device)
+
+
+def lora_max_norm(slab, shadow, table, max_norm, norms, factors, stats) -> Op:
+    """Max-norm regularisation over the modules of ``table`` (`lora_norm_table`): norms[m] = scale_m |up_m down_m|_F before
+    scaling, modules above ``max_norm`` pulled back onto it (slab and bf16 shadow, factors[m] on both matrices), stats =
+    {modules scaled, mean norm, max norm (after scaling), non-finite modules}.  ``max_norm == 0``: measure only."""
+    M = table.numel() // C.sizeof(hip.LoraNormModule)
+    if table.dtype != torch.uint8 or table.numel() != M * C.sizeof(hip.LoraNormModule):
+        raise ValueError("lora_max_norm: table must come from lora_norm_table")
+    if slab.dtype != torch.float32 or shadow.dtype != torch.bfloat16 or shadow.numel() != slab.numel():
+        raise ValueError("lora_max_norm: slab must be fp32 and shadow its bf16 image of the same length")
+    for name, t, need in (("norms", norms, M), ("factors", factors, M), ("stats", stats, 4)):
+        if t.dtype != torch.float32 or t.numel() < need:
+            raise ValueError(f"lora_max_norm: {name} must hold {need} fp32 values")
+    return Op("leco_lora_max_norm", (ptr(slab), ptr(shadow), slab.numel(), ptr(table), M, float(max_norm), ptr(norms),
+                                     ptr(factors), ptr(stats)), keep=(slab, shadow, table, norms, factors, stats))
 
 
 def cast_f32_bf16(x, y, n) -> Op:

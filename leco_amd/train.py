@@ -21,7 +21,8 @@ save cadence and file names.  The per-step arithmetic (train_lora.py:141-290) is
 
 Optional, both on the device: ``max_grad_norm`` clips the gradient by its global norm between 6 and 7 (one reduction launch
 that rewrites the optimizers' device-side grad_scale); ``accumulate`` = A sums the gradients of A steps in a second slab and
-runs 6 and 7 once per group.
+runs 6 and 7 once per group; ``scale_weight_norms`` pulls every LoRA module whose effective update has grown past that
+Frobenius norm back onto it after 7 (max-norm regularisation, one launch on the slab: `leco_lora_max_norm`).
 
 Nothing in a step synchronises with the host; ``loss`` is a device scalar.
 """
@@ -131,7 +132,7 @@ class FusedStep:
     def __init__(self, unet, network: LoRANetwork, scheduler, max_denoising_steps: int = 50, lr: float = 1e-4,
                  betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, world_size: int = 1,
                  process_group=None, optimizer="adamw", dedup: bool = False, prodigy: Optional[dict] = None,
-                 max_grad_norm: Optional[float] = None, accumulate: int = 1):
+                 max_grad_norm: Optional[float] = None, accumulate: int = 1, scale_weight_norms: Optional[float] = None):
         """``optimizer``: "adamw" / "adam" (fused leco_adamw; adam = no decoupled decay), "lion" (fused leco_lion),
         "prodigy" (fused leco_prodigy; ``prodigy``: its keywords, `PRODIGY_DEFAULTS` -- ``betas`` / ``eps`` default to
         this constructor's arguments, ``weight_decay`` to Prodigy's own 0 unless the dict carries it; ``lr`` is the
@@ -140,7 +141,16 @@ class FusedStep:
         ``max_grad_norm``: clip the (all-reduced, averaged) gradient to this global L2 norm before the optimizer, on the
         device (`leco_grad_clip` rewrites the optimizers' grad_scale); 0 = measure only (`grad_stats`); None = off, no launch.
         ``accumulate`` = A > 1: `step` adds its gradient to ``network.grad_acc`` and only every A-th call all-reduces and
-        applies the optimizer, on the mean of the group (`flush` applies a partial group)."""
+        applies the optimizer, on the mean of the group (`flush` applies a partial group).
+        ``scale_weight_norms``: max-norm regularisation -- after every optimizer step each module whose effective update
+        ``scale * lora_up @ lora_down`` has a Frobenius norm above this bound is scaled back onto it, on the device
+        (`leco_lora_max_norm`, `LoRANetwork.apply_max_norm`'s rule; `weight_norm_stats`); 0 = measure only; None = off, no
+        launch and no allocation."""
+        if scale_weight_norms is not None and not float(scale_weight_norms) >= 0.0:
+            raise ValueError(f"scale_weight_norms must be >= 0 (0: measure only) or None, got {scale_weight_norms!r}")
+        if scale_weight_norms is not None and (network.strict_reference or isinstance(optimizer, StrictReferenceOptimizer)):
+            raise ValueError("scale_weight_norms cannot be combined with --strict_reference: the reference has no such step, and "
+                             "that mode's bf16 master weights would need a rounding rule of their own")
         if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
             raise ValueError(f"max_grad_norm must be >= 0 (0: measure only) or None, got {max_grad_norm!r}")
         if int(accumulate) != accumulate or accumulate < 1:
@@ -210,6 +220,9 @@ class FusedStep:
         self._token = next(FusedStep._tokens)      # names this object's private launch lists on plans the engine shares by shape
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self._grad_stats = torch.zeros(4, dtype=torch.float32, device=dev) if max_grad_norm is not None else None
+        self.scale_weight_norms = None if scale_weight_norms is None else float(scale_weight_norms)
+        if self.scale_weight_norms is not None:
+            network.norm_buffers()                 # the module table is uploaded here, not inside the first step
         self.accumulate = int(accumulate)
         self.pending = 0                           # micro-steps summed in network.grad_acc since the last optimizer step
         if self.accumulate > 1:
@@ -608,7 +621,19 @@ class FusedStep:
                 group["lr"] = lr
             self.optimizer.step()
             net.sync_shadow()
+        if self.scale_weight_norms is not None:
+            # max-norm regularisation on the stepped slab and its shadow: one launch, the decisions stay on the device
+            net._max_norm_op(self.scale_weight_norms).run()
         net.mark_updated()
+
+    def weight_norm_stats(self) -> dict:
+        """{keys_scaled, avg_norm, max_norm, nonfinite} of the last optimizer step (`leco_lora_max_norm`: the modules pulled
+        back, the mean and the maximum of the module norms after that, the modules whose norm was not finite).  Copies them
+        from the device, i.e. waits for the queued steps: for tests and logging."""
+        if self.scale_weight_norms is None:
+            raise RuntimeError("this FusedStep was built without scale_weight_norms (0 measures without scaling)")
+        k, avg, top, bad = self.net.norm_buffers()[3].cpu().tolist()
+        return dict(zip(ops.WEIGHT_NORM_STATS_FIELDS, (int(k), avg, top, int(bad))))
 
     def grad_stats(self) -> dict:
         """{norm, coef, nonfinite} of the last optimizer step's gradient (`leco_grad_clip`: the norm of the averaged,
@@ -791,6 +816,9 @@ def train(config: RootConfig, prompts: List[PromptSettings], device: Optional[to
     ``native_text_encoder``: the prompts are encoded by `leco_amd.clip` instead of the ``transformers`` models (bf16 only)."""
     if dedup is None:
         dedup = not strict_reference and os.environ.get("LECO_DEDUP", "1") not in ("", "0")
+    if strict_reference and config.train.scale_weight_norms is not None:
+        raise ValueError("train.scale_weight_norms cannot be combined with --strict_reference: the reference has no such step, "
+                         "and that mode's bf16 master weights would need a rounding rule of their own")
     rank, world, local = init_distributed()
     if device is None:
         device = torch.device(f"cuda:{local}" if torch.cuda.is_available() else "cpu")
@@ -885,6 +913,7 @@ def train(config: RootConfig, prompts: List[PromptSettings], device: Optional[to
                       weight_decay=optimizer_kwargs.get("weight_decay", wd_default), world_size=world,
                       optimizer=fused_opt, dedup=dedup, max_grad_norm=config.train.max_grad_norm,
                       accumulate=config.train.gradient_accumulation_steps,
+                      scale_weight_norms=config.train.scale_weight_norms,
                       prodigy={k: v for k, v in optimizer_kwargs.items() if k not in ("betas", "eps")}
                       if fused_opt == "prodigy" else None)
     # LR schedule: drive torch's own scheduler objects on a dummy parameter so the values are exact
@@ -981,13 +1010,20 @@ def train(config: RootConfig, prompts: List[PromptSettings], device: Optional[to
         if gstat is not None and gstat["nonfinite"] > 0:
             raise FloatingPointError(f"iteration {i}: {gstat['nonfinite']} non-finite element(s) in the LoRA gradient of the last "
                                      f"optimizer step (norm {gstat['norm']}); the weights are no longer usable")
+        # ... and, with scale_weight_norms, the module norms the last optimizer step left
+        wstat = (fused.weight_norm_stats() if fused.scale_weight_norms is not None and fused.opt_step and (show or wandb is not None)
+                 else None)
         if show:
             pbar.set_description(f"Loss*1k: {loss.item() * 1000:.4f}" + ("" if dlr is None else f" d*lr: {dlr:.3e}")
-                                 + ("" if gstat is None else f" |g|: {gstat['norm']:.2e}" + ("*" if gstat["coef"] < 1 else "")))
+                                 + ("" if gstat is None else f" |g|: {gstat['norm']:.2e}" + ("*" if gstat["coef"] < 1 else ""))
+                                 + ("" if wstat is None else f" |w|: {wstat['avg_norm']:.2e}/{wstat['max_norm']:.2e}"
+                                    + (f"*{wstat['keys_scaled']}" if wstat["keys_scaled"] else "")))
         if wandb is not None:
             wandb.log({"loss": loss.item(), "iteration": i, "lr": lr_scheduler.get_last_lr()[0],
                        **({} if dlr is None else {"d*lr": dlr}),
-                       **({} if gstat is None else {"grad_norm": gstat["norm"], "clip_coef": gstat["coef"]})})
+                       **({} if gstat is None else {"grad_norm": gstat["norm"], "clip_coef": gstat["coef"]}),
+                       **({} if wstat is None else {"avg_key_norm": wstat["avg_norm"], "max_key_norm": wstat["max_norm"],
+                                                    "keys_scaled": wstat["keys_scaled"]})})
         _dummy.step()
         lr_scheduler.step()
         if i % config.save.per_steps == 0 and i != 0 and i != config.train.iterations - 1:
